@@ -16,7 +16,14 @@ end (`--dtype float32`: exact-fp32 matrix cores in extractor and fit) and `value
 fp32 accumulation), three pipelined images each inside the same timed bracket.  `parity` is measured in the same
 process: the HIP chain against the CPU oracle chain on the sample the CPU baseline is timed on.
 
+A plain run measures `value` only: set-up, `--warmup` untimed images, `--steps` timed images (with the in-region per-kernel
+table and `roofline` of the three probed kernels), the outputs if `--dump-outputs DIR` is given, the JSON line.  Everything
+else above -- the serial timers and isolated per-kernel table of one un-pipelined image, `value_fp32_fit`, `value_fp32`,
+`value_fp32_matmul_high`, the ViT-L/14 and stage-2 legs, `cpu_baseline` and `parity` -- runs only with `--full` (each of
+them can still be left out there by its --no-* flag).
+
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -88,8 +95,8 @@ def parse():
     p.add_argument("--tune", type=str, default="", help="developer knobs: key=value,... for dvt_tune_set")
     p.add_argument("--fit-batch", type=int, default=4,
                    help="images whose fits share launches (dvt_fit_run_batched); 1 = one fit at a time.  4 (default since round "
-                        "6): +0.9 % images/s at these flags on one box (2.957 / 2.960 against 2.931 / 2.932, "
-                        "profiles/r06/r06c_*), +1.8 % at --steps 40 (profiles/r05/r05j_*), for 3.2 GB of feature store per "
+                        "6): +0.9 %% images/s at these flags on one box (2.957 / 2.960 against 2.931 / 2.932, "
+                        "profiles/r06/r06c_*), +1.8 %% at --steps 40 (profiles/r05/r05j_*), for 3.2 GB of feature store per "
                         "extra image in flight")
     p.add_argument("--fit-dtype", default="bfloat16", choices=["bfloat16", "float32"],
                    help="operand precision of the fit's MLP GEMMs for `value` (the reference's --dtype; bfloat16 = "
@@ -106,7 +113,21 @@ def parse():
                    help="test hook: join the N-rank process group over gloo, run the timed bracket on no work, print one line")
     p.add_argument("--pipeline-depth", type=int, default=2,
                    help="images in flight per GPU (1 = strictly serial reference flow)")
+    p.add_argument("--full", action="store_true",
+                   help="also run every measurement beyond `value`: serial timers and isolated per-kernel table, the other "
+                        "fit precision, --dtype float32 and --fp32_matmul high, the ViT-L/14 and stage-2 legs, the CPU "
+                        "baseline and parity (off by default: a plain run times the headline images only)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the two arrays the last timed image handed its caller (raw and "
+                        "denoised features, float32) as DIR/raw_features.npy and DIR/denoised_features.npy (rank 0)")
     return p.parse_args()
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one float32 .npy file per array, named by its key."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(arr, dtype=np.float32))
 
 
 def stage1_args(a):
@@ -420,29 +441,41 @@ def main():
 
     st.run(jobs(a.warmup), total=a.warmup)
     probes = [] if a.no_probes else ["adam", "vit_gemm", "vit_attn", "fit_gemm", "grid"]
-    # un-pipelined passes over one image, outside the timed region.  First with every probe OFF: the reference's two
-    # timers (main_img_denoising.py:341, :355) -- round 4 took them with all five probes on and the ~15 k event pairs of a
-    # fit inflated t_fit from 93 to 115 ms.  Then once more with the probes on: per-kernel durations WITHOUT a second
-    # stream competing for the GPU.
-    _lib.prof_enable([])
-    st.process(lambda slot: None)
-    split = st.timings[-1]
-    _lib.prof_enable(probes)
-    st.process(lambda slot: None)
-    prof_iso = {n: _lib.prof_collect(n) for n in probes}
+    split, prof_iso = None, None
+    if a.full:
+        # un-pipelined passes over one image, outside the timed region.  First with every probe OFF: the reference's two
+        # timers (main_img_denoising.py:341, :355) -- round 4 took them with all five probes on and the ~15 k event pairs of a
+        # fit inflated t_fit from 93 to 115 ms.  Then once more with the probes on: per-kernel durations WITHOUT a second
+        # stream competing for the GPU.
+        _lib.prof_enable([])
+        st.process(lambda slot: None)
+        split = st.timings[-1]
+        _lib.prof_enable(probes)
+        st.process(lambda slot: None)
+        prof_iso = {n: _lib.prof_collect(n) for n in probes}
     # inside the timed region only the three heavy kernels are probed (~2.5 k event pairs per
     # image); probing all ~15 k small fit launches costs ~100 us/step (measured) and would
     # distort the metric
     probes = [n for n in probes if n in ("adam", "vit_gemm", "vit_attn")]
     _lib.prof_enable(probes)
-    n_done, elapsed, per_rank = D.timed(lambda: st.run(jobs(a.steps), on_result=write_pair, total=a.steps), device)
+    last = {}  # the last timed image's host outputs (its slot's pinned buffers: nothing rewrites them before the next run)
+
+    def on_timed(tag, raw_h, den_h):
+        write_pair(tag, raw_h, den_h)
+        if tag == a.steps - 1:
+            last["raw_features"], last["denoised_features"] = raw_h, den_h
+
+    n_done, elapsed, per_rank = D.timed(lambda: st.run(jobs(a.steps), on_result=on_timed, total=a.steps), device)
     npy_bytes = written[0]
     assert n_done == a.steps
     prof = {n: _lib.prof_collect(n) for n in probes}
     _lib.prof_enable([])
+    if a.dump_outputs and rank == 0:
+        assert len(last) == 2, "the last timed image delivered no outputs"
+        dump_outputs(a.dump_outputs, last)
     other = "float32" if a.fit_dtype == "bfloat16" else "bfloat16"
     second = None
-    if not a.no_fp32_fit:  # the other fit precision, same timed bracket, fewer images
+    if a.full and not a.no_fp32_fit:  # the other fit precision, same timed bracket, fewer images
         k2 = max(2, a.steps // 3)
         set_fit_dtype(other)
         st.run(jobs(1), total=1)
@@ -452,7 +485,7 @@ def main():
                   "t_fit_s_serial": st.timings[-1]["t_fit"]}
         set_fit_dtype(a.fit_dtype)
     full_fp32 = None
-    if not a.no_fp32_fit and world == 1 and a.model in IMAGE_CEILINGS:
+    if a.full and not a.no_fp32_fit and world == 1 and a.model in IMAGE_CEILINGS:
         # the reference's DEFAULT precision end to end (--dtype float32: fp32 extractor + fp32 fit), the same pipelined
         # driver inside the same timed bracket, 5 images (exact-fp32 matrix cores: 1/16 of the bf16 rate; 3 images until
         # round 4 -- with ~2 s per image the pipeline's fill + drain weighed 4 % of a 3-image bracket)
@@ -484,7 +517,7 @@ def main():
         shutil.rmtree(save_root, ignore_errors=True)
     pipe_depth, launch_views = a.pipeline_depth, st.vit_launch_views(a.views + 1)
     large = None
-    if not a.no_vit_large and world == 1 and a.model in IMAGE_CEILINGS and a.model != VIT_LARGE:
+    if a.full and not a.no_vit_large and world == 1 and a.model in IMAGE_CEILINGS and a.model != VIT_LARGE:
         del st  # ViT-B slots and workspace (~22 GB) are not needed any more
         torch.cuda.empty_cache()
         try:
@@ -493,7 +526,7 @@ def main():
             large = {"error": repr(exc)}
 
     s2 = None
-    if not a.no_stage2 and world == 1 and a.model in IMAGE_CEILINGS:
+    if a.full and not a.no_stage2 and world == 1 and a.model in IMAGE_CEILINGS:
         try:
             s2 = stage2_leg(device, D)
         except Exception as exc:  # an extra leg must never take the bench line down
@@ -532,8 +565,8 @@ def main():
                              "with the IEEE replay)"),
                 "extractor": "LayerNorm folded into the qkv / fc1 GEMMs (bf16 path); LayerNorm kernels in the fp32 path",
                 "weights": "random init (no network for checkpoints)",
-                "t_extract_s_serial": split["t_extract"], "t_fit_s_serial": split["t_fit"],
-                "serial_timers": "one strictly serial image with every profiling probe OFF",
+                **({"t_extract_s_serial": split["t_extract"], "t_fit_s_serial": split["t_fit"],
+                    "serial_timers": "one strictly serial image with every profiling probe OFF"} if split is not None else {}),
                 "pipeline_depth": pipe_depth, "fit_batch": a.fit_batch,
                 "extract_launch_views": launch_views,
                 "images_per_rank": a.steps, "parallelism": f"images sharded over {world} GPU(s), no collective",
@@ -594,7 +627,8 @@ def main():
             # region (profiles/<round>/final/pipe_kernel_stats.txt); `kernels_isolated` (one serial image, one stream)
             # agrees with rocprofv3's serial table.
             out["kernels"] = kern  # inside the timed (pipelined) region
-            out["kernels_isolated"] = kernel_table(prof_iso, 1)  # serial pass, one stream
+            if prof_iso is not None:
+                out["kernels_isolated"] = kernel_table(prof_iso, 1)  # serial pass, one stream
             out["kernels_timing"] = "hipEvent brackets on the launch stream (see profiles/ for the rocprofv3 tables)"
             dom = max(kern, key=lambda k: kern[k]["ms_per_image"])
             out["roofline"] = {"kernel": dom, **{k: kern[dom][k] for k in
@@ -612,7 +646,7 @@ def main():
             out["image_level"] = {"per_gpu_images_per_s": per_gpu, "ceiling_serial": ser, "ceiling_overlapped": ovl,
                                   "frac_of_serial_ceiling": per_gpu / ser, "frac_of_overlapped_ceiling": per_gpu / ovl,
                                   "definition": "SURVEY.md 8(d): 233.1 TFLOP / 2.5 PF/s + 0.549 TB / 8 TB/s per image"}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 out["cpu_baseline"], out["parity"] = cpu_baseline_and_parity(a, vit, device)
             except Exception as exc:  # the baseline must never take the bench line down

@@ -103,11 +103,12 @@ def test_wrapper_loads_a_timm_layout_checkpoint(tmp_path):
     assert not any(m.startswith("samvit") for m in MODEL_LIST)
 
 
-def test_stage1_flag_table_keeps_the_reference_defaults():
+def test_stage1_flag_table_keeps_the_reference_defaults(golden_dir):
     """EVERY flag of the reference's argparse table (main_img_denoising.py:152-208) with its default, plus
     this build's extras, whose defaults must not change what the reference's flags mean: --fp32_matmul highest (exact
     fp32), --fit_batch 0 (auto), --extract_launch_views 0 (auto; the reference's --extract_bsz 32 is a DataLoader batch
     and keeps its name and default)."""
+    import json
     from dvt_amd import stage1
     a = stage1.get_args([])
     ref = {"model": "vit_base_patch14_dinov2.lvd142m", "stride_size": 14, "layer_depth_ratio": 1.0,
@@ -118,13 +119,11 @@ def test_stage1_flag_table_keeps_the_reference_defaults():
     for k, v in ref.items():
         assert getattr(a, k) == v, (k, getattr(a, k), v)
     assert tuple(a.input_size) == (518, 518)
-    # the table above is complete: every option string the reference's parser declares is in it (parsed from the
-    # reference's source when it is present -- this container; the GPU box has no /root/reference)
-    ref_src = "/root/reference/main_img_denoising.py"
-    if os.path.exists(ref_src):
-        import re
-        flags = set(re.findall(r'"--([a-z_0-9]+)"', open(ref_src).read()))
-        assert flags == set(ref) | {"input_size"}, flags ^ (set(ref) | {"input_size"})
+    # the table above is complete: every option string the reference's parser declares is in it (the list of those
+    # option strings is a committed fixture, tests/golden/stage1_reference_flags.json)
+    with open(os.path.join(golden_dir, "stage1_reference_flags.json")) as fh:
+        flags = set(json.load(fh)["flags"])
+    assert flags == set(ref) | {"input_size"}, flags ^ (set(ref) | {"input_size"})
     assert a.fp32_matmul == "highest" and a.fit_batch == 0 and a.extract_launch_views == 0
     assert stage1.get_args(["--dtype", "float32", "--fp32_matmul", "high"]).fp32_matmul == "high"
     import pytest

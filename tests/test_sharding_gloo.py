@@ -188,3 +188,13 @@ def test_bench_rank_checks_its_world_size():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rendezvous-only"],
                        env=env, capture_output=True, text=True)
     assert r.returncode != 0 and "--gpus 2 but WORLD_SIZE=1" in r.stderr
+
+
+def test_bench_help_names_full_and_dump_outputs():
+    """`--full` (every measurement beyond `value`) and `--dump-outputs DIR` are on the command line and `--help` prints them."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], env=_bench_env(), capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-800:]
+    assert "--full" in r.stdout and "--dump-outputs DIR" in r.stdout

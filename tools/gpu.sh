@@ -3,7 +3,7 @@
 #   /usr/local/graft/bin/gpurun --timeout 1200 -- 'bash tools/gpu.sh <stage> [<stage> ...]'
 # Stages (outputs under gpurun_out/<tag>/, tag = $DVT_TAG or "run"):
 #   suite        full `pytest -m gpu`                         smoke     __graft_entry__.smoke()
-#   bench        the default bench line                       bench:<args>  bench.py with extra args (":" -> " ")
+#   bench        the bench line with --full                   bench:<args>  the same with extra args (":" -> " ")
 #   prof         rocprofv3 --kernel-trace --stats of a serial and a pipelined bench run (kernel tables kept)
 #   pmc          FETCH_SIZE / WRITE_SIZE / SQ passes (separate rocprofv3 --pmc runs) over tools/pmc_target.py
 #   py:<file>[:args]   python <file> args...                  test:<pytest node or -k expr>
@@ -29,7 +29,7 @@ for stage in "$@"; do
       timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; echo "smoke rc=$?"; tail -4 $O/smoke.txt ;;
     bench)
       n_bench=$((n_bench+1)); f=$O/bench${n_bench}_$(echo "$arg" | tr -c 'A-Za-z0-9=' '_' | rev | cut -c1-50 | rev).log
-      timeout 1500 python bench.py $(echo "$arg" | tr ':' ' ') > $f 2>&1; echo "bench rc=$?"
+      timeout 1500 python bench.py --full $(echo "$arg" | tr ':' ' ') > $f 2>&1; echo "bench rc=$?"
       tail -1 $f > ${f%.log}.json; python - "${f%.log}.json" <<'PY'
 import json, sys
 try:
@@ -44,8 +44,8 @@ PY
       ;;
     prof)
       cd /tmp
-      timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_serial -o serial -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-probes --no-fp32-fit --no-vit-large --no-stage2 --pipeline-depth 1 > $O/prof_serial.log 2>&1
-      timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_pipe -o pipe -- python $R/bench.py --steps 12 --warmup 4 --no-cpu-baseline --no-probes --no-fp32-fit --no-vit-large --no-stage2 > $O/prof_pipe.log 2>&1
+      timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_serial -o serial -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-probes --no-fp32-fit --no-vit-large --no-stage2 --pipeline-depth 1 > $O/prof_serial.log 2>&1
+      timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_pipe -o pipe -- python $R/bench.py --full --steps 12 --warmup 4 --no-cpu-baseline --no-probes --no-fp32-fit --no-vit-large --no-stage2 > $O/prof_pipe.log 2>&1
       cd $R
       for n in serial pipe; do python tools/rocpd_stats.py $(find $O/prof_$n -name '*.db' | head -1) > $O/${n}_kernel_stats.txt; tail -1 $O/prof_$n.log | cut -c1-120; done
       rm -rf $O/prof_serial $O/prof_pipe
