@@ -102,6 +102,9 @@ struct GemmBArgs {
   float2* st_part;         // [N / 64][M] (sum, sum of squares)
   float q_scale;      // EPI_QKV: the q columns (n < dim) leave multiplied by this (log2(e) / 8 for the log2-domain attention
                       // kernel); 0 = as they are
+  int vt_rows;        // EPI_QKV / EPI_QKV_X3: batch * s_pad, the real token rows.  The phantom rows behind them (up to the
+                      // whole 256-row tile) store their q | k but no V^T: `vt` holds `batch` images (their image index would
+                      // run past it -- by up to 7 images at s_pad = 32)
   int dim_ok_sq;      // 256-wide tiles may be used (no q|k|v boundary inside a tile)
   int lda, ldw;       // leading dimensions (elements) of A and W; 0 = K
   double work;        // profiling probe: ALGORITHMIC flops of this launch (0: 2*M*N*K of the padded shape)
@@ -318,6 +321,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmBArgs& p, f32x4 (&acc)[4
         for (int r = 0; r < 4; ++r) p.x[(size_t)(mrow + r) * p.N + n] = v[r];
       } else if (IS_QKV(EPI) && n0 >= 2 * p.dim) {
         // V: transposed store vt[b][h][d][s], the lane's 4 rows are 4 consecutive tokens
+        // (a phantom row stores no V^T: vt_rows % 4 == 0, so a lane's 4 rows are all real or all phantom)
+        if (mrow >= p.vt_rows) continue;
         const int f = n - 2 * p.dim, h = f >> 6, d = f & 63;
         const int b = mrow / p.s_pad, s = mrow - b * p.s_pad;
         uint2 pk;
@@ -491,8 +496,10 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmBArgs& p, f32x4 (&ac
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // each wave re-reads its own block only
     const int f0 = nb - 2 * p.dim, hh = f0 >> 6;        // (the block is one head's 64 features: dim_ok_sq / 64-aligned)
-    // the image of THIS lane's 8 tokens: a block may straddle two images (s_pad % 64 != 0), an 8-token chunk never (s_pad % 8 == 0)
+    // the image of THIS lane's 8 tokens: a block may straddle two images (s_pad % 64 != 0), an 8-token chunk never (s_pad % 8 == 0);
+    // a chunk of phantom rows (at or behind vt_rows, also a multiple of 8) stores nothing -- its image would lie behind `vt`
     const int trow = mbv + tc * 8, bimg = trow / p.s_pad, s0 = trow - bimg * p.s_pad;
+    const bool vst = trow < p.vt_rows;
     bf16_t* const vrow = p.vt + ((size_t)(bimg * p.heads + hh) * 64) * p.s_pad + s0;
 #pragma unroll
     for (int it = 0; it < NPASS; ++it) {
@@ -511,13 +518,13 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmBArgs& p, f32x4 (&ac
       }
       typedef unsigned u32x4v_t __attribute__((ext_vector_type(4)));
       const u32x4v_t hi = {pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
-      *reinterpret_cast<u32x4v_t*>(vrow + (size_t)d * p.s_pad) = hi;
+      if (vst) *reinterpret_cast<u32x4v_t*>(vrow + (size_t)d * p.s_pad) = hi;
       if constexpr (EPI == EPI_QKV_X3) {
         u32x4v_t lo;
 #pragma unroll
         for (int q = 0; q < 4; ++q)
           lo[q] = pack2(v[2 * q] - __uint_as_float(hi[q] << 16), v[2 * q + 1] - __uint_as_float(hi[q] & 0xffff0000u));
-        *reinterpret_cast<u32x4v_t*>(p.vt_lo + (vrow - p.vt) + (size_t)d * p.s_pad) = lo;
+        if (vst) *reinterpret_cast<u32x4v_t*>(p.vt_lo + (vrow - p.vt) + (size_t)d * p.s_pad) = lo;
       }
     }
     return;
@@ -1320,6 +1327,19 @@ int launch_gemm(const GemmBArgs& a0, hipStream_t s) {
   if (!a.lda) a.lda = a.K;
   if (!a.ldw) a.ldw = a.K;
   a.dim_ok_sq = (!IS_QKV(EPI)) || (a.dim % 256 == 0);
+  // V^T: vt_rows real rows of whole images, a multiple of 8 (the LDS-staged epilogue's 8-token chunks)
+  if (IS_QKV(EPI) && (a.s_pad <= 0 || a.s_pad % 8 || a.vt_rows <= 0 || a.vt_rows % a.s_pad || a.vt_rows > a.M))
+    return DVT_E_BADARG;
+  bool sq = g_vit_gemm_variant >= 4;  // (lab: 5..12 are variants of the same tile)
+#ifdef DVT_LAB
+  sq = sq || g_vit_gemm_variant == 0;
+#endif
+  sq = sq && a.M % 256 == 0 && a.N % 256 == 0 && a.dim_ok_sq && a.K >= 2 * GBK && (a.K / GBK) % 2 == 0;  // (8p: k-tiles in pairs)
+  // The folded LayerNorm's consumer side (ln_stats) lives in the LDS-staged epilogues (256-row tiles), its producer side (xb /
+  // st_part) in the 256 x 256 residual epilogue: a launch that would take another kernel is refused, not silently unfolded
+  if (a.ln_stats != nullptr && !(sq || (a.M % G2_BM == 0 && g_vit_gemm_variant != 1))) return DVT_E_BADARG;
+  if ((a.xb != nullptr || a.st_part != nullptr) && !(sq && EPI == EPI_RESID && a.xb != nullptr && a.st_part != nullptr))
+    return DVT_E_BADARG;
   {
     const int nt = a.N / GBN;
     int g = g_vit_group_bytes / (GBN * a.K * 2);
@@ -1328,11 +1348,7 @@ int launch_gemm(const GemmBArgs& a0, hipStream_t s) {
     a.group = g;
   }
   DvtProbeScope probe(DVT_PROBE_VIT_GEMM, s, a.work > 0.0 ? a.work : 2.0 * a.M * a.N * a.K);
-  bool sq = g_vit_gemm_variant >= 4;  // (lab: 5..12 are variants of the same tile)
-#ifdef DVT_LAB
-  sq = sq || g_vit_gemm_variant == 0;
-#endif
-  if (a.M % 256 == 0 && a.N % 256 == 0 && a.dim_ok_sq && a.K >= 2 * GBK && (a.K / GBK) % 2 == 0 && sq) {  // (8p: k-tiles in pairs)
+  if (sq) {
     const int nt = a.N / 256;
     // N tiles per group: W slices of a group stay L2-resident, but never fewer than 3 tiles share
     // an A panel (K = 3072: one tile per group re-read A three times from HBM, 1.03 -> 1.23 PF/s)
@@ -2395,7 +2411,9 @@ int64_t vit_carve(const DvtVitConfig* c, int batch, char* base, VitWork* w) {
   // (+ 128 rows: where s_pad is not a multiple of 128 the attention kernel's last query block / key tile of the LAST image read
   // up to 127 rows past batch * s_pad -- never used: masked keys, unstored queries -- which T does not always cover)
   t.qk = (bf16_t*)take((T + 128) * 2 * c->dim * 2);
-  t.vt = (bf16_t*)take(((int64_t)batch + 1) * c->s_pad * c->dim * 2);  // the phantom rows' V^T lands in image `batch`
+  // (the phantom rows store no V^T (GemmBArgs::vt_rows): `batch` images are what is written and read; the spare image keeps
+  // the layout of the workspace as it was)
+  t.vt = (bf16_t*)take(((int64_t)batch + 1) * c->s_pad * c->dim * 2);
   t.hid = (bf16_t*)take(T * c->mlp_dim * 2);
   t.col = (bf16_t*)take(T * c->k_patch * 2);
   t.xb = (bf16_t*)take(T * c->dim * 2);
@@ -2613,9 +2631,54 @@ extern "C" int dvt_vit_gemm_f32out(const void* a_in, const void* w, const float*
   return launch_gemm<EPI_F32>(a, (hipStream_t)stream);
 }
 
+// The qkv GEMM exactly as dvt_vit_forward launches it (EPI_QKV): q | k into qk [m, 2 dim], V^T into vt [batch, heads, 64, s_pad]
+extern "C" int dvt_vit_gemm_qkv(const void* x, const void* w, const float* b, void* qk, void* vt, int m, int dim, int heads,
+                                int s_pad, int batch, const void* ln_stats, const float* ln_cs, float q_scale, void* stream) {
+  if (!x || !w || !qk || !vt || batch <= 0 || heads <= 0 || dim != heads * 64 || s_pad <= 0 || s_pad % 32 ||
+      (ln_stats == nullptr) != (ln_cs == nullptr))
+    return DVT_E_BADARG;
+  if ((long long)m != ((long long)batch * s_pad + 255) / 256 * 256) return DVT_E_BADARG;
+  if (ln_stats != nullptr && (m % 256 || (3 * dim) % 256 || b == nullptr)) return DVT_E_BADARG;  // the forward's condition
+  GemmBArgs a{};
+  a.A = (const bf16_t*)x; a.W = (const bf16_t*)w; a.M = m; a.N = 3 * dim; a.K = dim;
+  a.bias = b; a.out = (bf16_t*)qk; a.vt = (bf16_t*)vt;
+  a.ln_stats = (const float2*)ln_stats; a.ln_cs = ln_cs;
+  a.dim = dim; a.heads = heads; a.s_pad = s_pad; a.vt_rows = batch * s_pad;
+  a.q_scale = q_scale;
+  return launch_gemm<EPI_QKV>(a, (hipStream_t)stream);
+}
+
+// xb = bf16(x) and two-pass (mean, rstd) of every row: the kernel behind the patch embedding of the folded forward
+extern "C" int dvt_vit_ln_cast_stats(const float* x, void* xb, void* stats, int rows, int dim, float eps, void* stream) {
+  if (!x || !xb || !stats || rows < 0 || dim <= 0 || dim % 4 || dim > 1024) return DVT_E_BADARG;
+  if (rows == 0) return 0;
+  hipLaunchKernelGGL(ln_cast_stats_kernel, dim3(dvt_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, (bf16_t*)xb,
+                     (float2*)stats, rows, dim, eps);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
+// The proj / fc2 GEMM of the folded forward: the residual epilogue that also writes xb = bf16(x) and the per-row partial sums
+// into part_scratch [n / 64][m] (float2), then ln_stats_finalize_kernel -> stats [m] (mean, rstd) of the new x
+extern "C" int dvt_vit_gemm_residual_stats(const void* a_in, const void* w, const float* b, const float* gamma, float* x,
+                                           void* xb, void* stats, void* part_scratch, int m, int n, int k, float eps,
+                                           void* stream) {
+  if (!a_in || !w || !gamma || !x || !xb || !stats || !part_scratch || m <= 0 || n <= 0) return DVT_E_BADARG;
+  GemmBArgs a{};
+  a.A = (const bf16_t*)a_in; a.W = (const bf16_t*)w; a.M = m; a.N = n; a.K = k;
+  a.bias = b; a.x = x; a.gamma = gamma;
+  a.xb = (bf16_t*)xb; a.st_part = (float2*)part_scratch;
+  const int rc = launch_gemm<EPI_RESID>(a, (hipStream_t)stream);  // (DVT_E_BADARG unless the 256 x 256 kernel takes it)
+  if (rc) return rc;
+  hipLaunchKernelGGL(ln_stats_finalize_kernel, dim3(dvt_cdiv(m, 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const float2*)part_scratch, n / 64, m, 1.0f / (float)n, eps, (float2*)stats);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
 // scratch of the bf16x3 attention (elements of bf16): q|k hi [m, 2 dim], q|k lo [m, 2 dim], V^T hi and lo
 // [batch + 1, heads, 64, s_pad] each; m = batch * s_pad rounded up to whole 256-row GEMM tiles (the fused qkv epilogue
-// writes those phantom rows, their V^T lands in image `batch`)
+// writes the q | k of those phantom rows but no V^T: images 0 .. batch - 1 of V^T hi / lo are written, image `batch` never)
 struct X3Scratch {
   long long m, ql, vh, vl, total;
 };
@@ -2643,7 +2706,8 @@ extern "C" int dvt_vit_gemm_gelu_x3(const void* a_in, const void* w, const float
 // (dvt_vit_attention_x3_scratch_bytes: the layout dvt_vit_attention_x3_presplit reads)
 extern "C" int dvt_vit_gemm_qkv_x3(const void* a_in, const void* w, const float* b, void* scratch, int m, int dim, int heads,
                                    int s_pad, int batch, int k, void* stream) {
-  if (!a_in || !w || !scratch || batch <= 0 || dim != heads * 64) return DVT_E_BADARG;
+  // s_pad % 128: what its one consumer, dvt_vit_attention_x3_presplit, takes -- checked here, before anything is written
+  if (!a_in || !w || !scratch || batch <= 0 || dim != heads * 64 || s_pad <= 0 || s_pad % 128) return DVT_E_BADARG;
   const X3Scratch L = x3_scratch(batch, heads, s_pad);
   if (m != L.m) return DVT_E_BADARG;  // whole 256-row tiles over batch * s_pad rows, exactly
   GemmBArgs a{};
@@ -2653,7 +2717,7 @@ extern "C" int dvt_vit_gemm_qkv_x3(const void* a_in, const void* w, const float*
   a.out_lo = a.out + L.ql;
   a.vt = a.out + L.vh;
   a.vt_lo = a.out + L.vl;
-  a.dim = dim; a.heads = heads; a.s_pad = s_pad;
+  a.dim = dim; a.heads = heads; a.s_pad = s_pad; a.vt_rows = batch * s_pad;
   return launch_gemm<EPI_QKV_X3>(a, (hipStream_t)stream);
 }
 
@@ -2890,7 +2954,7 @@ extern "C" int dvt_vit_forward(const DvtVitConfig* c, const DvtVitWeights* w, co
       a.A = fuse_ln ? k.xb : k.xn; a.W = (const bf16_t*)(fuse_ln ? bw.qkv_wf : bw.qkv_w); a.M = T; a.N = 3 * D; a.K = D;
       a.bias = fuse_ln ? bw.qkv_bf : bw.qkv_b; a.out = k.qk; a.vt = k.vt;
       if (fuse_ln) { a.ln_stats = k.stats; a.ln_cs = bw.qkv_cs; }
-      a.dim = D; a.heads = c->heads; a.s_pad = c->s_pad; a.n_tokens = c->n_tokens;
+      a.dim = D; a.heads = c->heads; a.s_pad = c->s_pad; a.n_tokens = c->n_tokens; a.vt_rows = batch * c->s_pad;
       a.work = 2.0 * rows * 3.0 * D * D;
       a.q_scale = log2q ? ATT_Q_PRESCALE : 0.f;
       DVT_TRY(launch_gemm<EPI_QKV>(a, s));

@@ -65,6 +65,9 @@ _lib.register_signatures({
     "dvt_vit_gemm_gelu_x3": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "dvt_vit_gemm_qkv_x3": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dvt_vit_forward_f32x3": (_I, [C.POINTER(VitConfig), C.POINTER(VitWeights), _P, _P, _I, _I, _P, _P]),
+    "dvt_vit_gemm_qkv": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, C.c_float, _P]),
+    "dvt_vit_ln_cast_stats": (_I, [_P, _P, _P, _I, _I, C.c_float, _P]),
+    "dvt_vit_gemm_residual_stats": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_float, _P]),
 })
 
 

@@ -85,7 +85,9 @@ int dvt_vit_struct_sizes(int64_t* h_out3); /* {DvtVitConfig, DvtVitBlockWeights,
 
 /* img [batch, 3, img_h, img_w] fp32 (already normalised) -> feat [batch, grid_h, grid_w, dim] fp32
  * = final-LayerNorm'ed patch tokens after blocks[0 .. n_blocks-1] (n_blocks = layer_index + 1).
- * `workspace` must be zero-filled ONCE by the caller before its first use (padding rows).   */
+ * `workspace` (dvt_vit_workspace_bytes) needs no initialisation: every byte the forward reads it has written first in the
+ * same call, or reads only as a masked key / unstored query of the attention -- zero-filled, NaN-filled or left over from
+ * another launch, the features are the same bit for bit (tests/test_gpu_vit_epilogues.py).  Nothing is written behind it. */
 int dvt_vit_forward(const DvtVitConfig* h_cfg, const DvtVitWeights* h_w, const float* img,
                     float* feat, int batch, int n_blocks, void* workspace, void* stream);
 
@@ -125,7 +127,8 @@ int dvt_vit_attention_x3(const float* qkv, float* out, void* scratch, int batch,
 /* The split-output epilogues dvt_vit_forward_f32x3 uses by default (dvt_tune_set(1, -522): fp32 outputs + split kernels):
  *   dvt_vit_gemm_gelu_x3: out3 bf16 [m, 3n] = [hi | hi | lo] of GELU(a . w^T + b), the next linear layer's A operand;
  *   dvt_vit_gemm_qkv_x3:  q | k (hi, lo) and V^T (hi, lo) written straight into the attention scratch; m must be
- *     batch * s_pad rounded up to 256;  dvt_vit_attention_x3_presplit then runs the attention kernel on that scratch. */
+ *     batch * s_pad rounded up to 256 and s_pad % 128 == 0 (else DVT_E_BADARG, nothing written);  the phantom rows
+ *     behind batch * s_pad get q | k but no V^T;  dvt_vit_attention_x3_presplit then runs the attention kernel on that scratch. */
 int dvt_vit_gemm_gelu_x3(const void* a_bf16, const void* w_bf16, const float* b, void* out3, int m, int n, int k,
                          void* stream);
 int dvt_vit_gemm_qkv_x3(const void* a_bf16, const void* w_bf16, const float* b, void* scratch, int m, int dim, int heads,
@@ -147,13 +150,31 @@ int dvt_vit_gemm_bias(const void* x, const void* w, const float* b, void* y, int
                       void* stream);
 /* the fc1 GEMM as the extractor launches it: y[m, n] (bf16) = GELU(rstd[m] * (x[m, :] . w'[n, :] - mean[m] * cs[n]) + b'[n]),
  * LayerNorm folded into the weights (ln_stats [m] float2 (mean, rstd), ln_cs [n]; both NULL: plain x . w^T + b);
- * gelu = 0 (and no fold): the bias epilogue.  m % 256 == n % 256 == k % 64 == 0 for the folded form. */
+ * gelu = 0 (and no fold): the bias epilogue.  m % 256 == n % 256 == k % 64 == 0 and a 256-row schedule (dvt_tune_set(1, 3)
+ * or 4, the default) for the folded form; DVT_E_BADARG otherwise. */
 int dvt_vit_gemm_lnfold(const void* x, const void* w, const float* b, void* y, int m, int n, int k,
                         const void* ln_stats, const float* ln_cs, int gelu, void* stream);
 /* x[m, n] (fp32, in place) += gamma[n] * (a[m, k] (bf16) . w[n, k]^T (bf16) + b[n]): the attention-proj /
  * fc2 GEMM with the LayerScale + residual epilogue (timm Block.forward: x = x + ls(f(norm(x)))) */
 int dvt_vit_gemm_residual(const void* a, const void* w, const float* b, const float* gamma, float* x,
                           int m, int n, int k, void* stream);
+/* The same with the folded LayerNorm's producer side, as dvt_vit_forward runs it: besides x, xb = bf16(new x) [m, n] and the
+ * per-row partial (sum, sum of squares) of every 64-column block into part_scratch (float2 [n / 64][m]), then
+ * stats[m] = (mean, rstd) of the new x rows (float2; ONE pass: var = E[x^2] - mean^2 in fp32, so rstd loses precision as
+ * mean^2 / var grows).  m % 256 == n % 256 == 0, k % 128 == 0 and the 256 x 256 schedule (dvt_tune_set(1, 4), the default);
+ * DVT_E_BADARG otherwise. */
+int dvt_vit_gemm_residual_stats(const void* a, const void* w, const float* b, const float* gamma, float* x, void* xb,
+                                void* stats, void* part_scratch, int m, int n, int k, float eps, void* stream);
+/* xb (bf16 [rows, dim]) = bf16(x fp32 [rows, dim]) and stats[rows] (float2) = (mean, rstd) in two passes: what the folded
+ * forward runs behind the patch embedding.  dim % 4 == 0, dim <= 1024. */
+int dvt_vit_ln_cast_stats(const float* x, void* xb, void* stats, int rows, int dim, float eps, void* stream);
+/* The qkv GEMM of dvt_vit_forward: x bf16 [m, dim] . w^T (bf16 [3 dim, dim]) + b, q columns times q_scale (0: as they are),
+ * q | k into qk bf16 [m, 2 dim], v TRANSPOSED per head into vt bf16 [batch, heads, 64, s_pad] (the layout dvt_vit_attention
+ * reads).  m = batch * s_pad rounded up to 256 (s_pad % 32 == 0): the phantom rows behind batch * s_pad get their q | k
+ * (qk holds m rows) but no V^T (nothing is written behind image batch - 1).  ln_stats / ln_cs non-NULL: the LayerNorm
+ * folded as in dvt_vit_gemm_lnfold (w, b the folded weights); needs 3 dim % 256 == 0 and a 256-row schedule (3 or 4). */
+int dvt_vit_gemm_qkv(const void* x, const void* w, const float* b, void* qk, void* vt, int m, int dim, int heads, int s_pad,
+                     int batch, const void* ln_stats, const float* ln_cs, float q_scale, void* stream);
 /* y (bf16) [rows, dim] = LayerNorm(x fp32 [rows, dim]) * w + b */
 int dvt_vit_layernorm(const float* x, const float* w, const float* b, void* y, int rows, int dim,
                       float eps, void* stream);
