@@ -1,0 +1,454 @@
+// Pieces of the stage-2 step that the stage-3 step (dvt_stage3.hip) runs as well: the row type of the row-local kernels,
+// LayerNorm backward, GELU, the fused attention-row kernels, the linear layers' forward / backward on the 128 x 128 x 32
+// exact-fp32 tile and the batched attention products.  Internal to the library (not part of the C ABI).
+//
+// Everything below lives in an anonymous namespace: each including translation unit gets its own copy of the kernels and of
+// the side stream with its two events (created once per process and translation unit).  The A/B switches are the process's,
+// defined in dvt_stage2.hip.
+#pragma once
+#include "dvt_common.h"
+
+// dvt_gemm_f32.hip: the fp32 extractor's 128 x 128 x 32 exact-fp32 MFMA tile (x . w^T + b, shapes per dvt_linear_big_ok)
+int dvt_linear_fwd_big(const float* x, const float* w, const float* b, float* y, int m, int n, int k, hipStream_t s);
+bool dvt_linear_big_ok(int m, int n, int k);
+bool dvt_linear_wgrad_big_ok(int rows, int n, int k);
+int dvt_linear_wgrad_big(const float* dy, const float* x, float* dw, float* db, int rows, int n, int k, int accumulate,
+                         hipStream_t s);
+extern int g_s2_fork_wgrad, g_s2_attn_rows, g_s2_fuse_softmax_bwd, g_s2_big_wgrad, g_s2_big_bwd, g_s2_big_fwd;
+
+namespace {
+
+#define S2_TRY(x)              \
+  do {                         \
+    const int rc__ = (x);      \
+    if (rc__ != 0) return rc__; \
+  } while (0)
+
+// ---- a row of C floats held by one wave: float4 index lane + 64 j, j < NJ -------------------------------
+template <int C>
+struct Row {
+  static constexpr int NJ = (C / 4 + 63) / 64;
+  float4 v[NJ];
+  __device__ __forceinline__ void load(const float* p, int lane) {
+    const float4* p4 = reinterpret_cast<const float4*>(p);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int i = lane + 64 * j;
+      v[j] = (i < C / 4) ? p4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+  __device__ __forceinline__ void store(float* p, int lane) const {
+    float4* p4 = reinterpret_cast<float4*>(p);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int i = lane + 64 * j;
+      if (i < C / 4) p4[i] = v[j];
+    }
+  }
+  __device__ __forceinline__ void zero() {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  __device__ __forceinline__ float sum() const {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
+    return wave_sum(s);
+  }
+};
+#define ROW_FOR(j, NJ) _Pragma("unroll") for (int j = 0; j < NJ; ++j)
+
+__device__ __forceinline__ float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+__device__ __forceinline__ float4 f4_sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
+__device__ __forceinline__ float4 f4_mul(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
+__device__ __forceinline__ float4 f4_scale(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
+__device__ __forceinline__ float f4_dot(float4 a, float4 b) { return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w); }
+
+// ==========================================================================================================
+// LayerNorm backward fused with the residual-path gradient:
+//   dx = dres + rstd * (g - mean_c(g) - xhat * mean_c(g * xhat)),  g = dy * gamma,  xhat = (x - mean) * rstd
+//   dgamma += sum_rows dy * xhat,  dbeta += sum_rows dy
+// A 256-thread block walks 32 rows (8 per wave), keeps the parameter-gradient partials in registers, reduces
+// the 4 waves through LDS and issues ONE atomic per column.
+// ==========================================================================================================
+template <int C>
+__global__ __launch_bounds__(256) void s2_ln_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                        const float* __restrict__ gamma, const float* __restrict__ dres,
+                                                        float* __restrict__ dx, float* __restrict__ dgamma,
+                                                        float* __restrict__ dbeta, int R) {
+  constexpr int NJ = Row<C>::NJ;
+  __shared__ float red[2][4][C];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  Row<C> gm, ag, ab;
+  gm.load(gamma, lane);
+  ag.zero();
+  ab.zero();
+  const int r0 = blockIdx.x * 32 + wave * 8;
+  for (int i = 0; i < 8; ++i) {
+    const int r = r0 + i;
+    if (r >= R) break;
+    const float mu = mean[r], rs = rstd[r];
+    Row<C> d, xv, o;
+    d.load(dy + (size_t)r * C, lane);
+    xv.load(x + (size_t)r * C, lane);
+    float s1 = 0.f, s2 = 0.f;
+    ROW_FOR(j, NJ) {
+      const int idx = lane + 64 * j;
+      const float4 xh = (idx < C / 4) ? f4_scale(f4_sub(xv.v[j], make_float4(mu, mu, mu, mu)), rs)
+                                      : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 g = f4_mul(d.v[j], gm.v[j]);
+      ag.v[j] = f4_add(ag.v[j], f4_mul(d.v[j], xh));
+      ab.v[j] = f4_add(ab.v[j], d.v[j]);
+      s1 += (g.x + g.y) + (g.z + g.w);
+      s2 += f4_dot(g, xh);
+      xv.v[j] = xh;
+      d.v[j] = g;
+    }
+    const float m1 = wave_sum(s1) * (1.0f / C), m2 = wave_sum(s2) * (1.0f / C);
+    if (dres) o.load(dres + (size_t)r * C, lane); else o.zero();
+    ROW_FOR(j, NJ) {
+      const float4 t = f4_sub(f4_sub(d.v[j], make_float4(m1, m1, m1, m1)), f4_scale(xv.v[j], m2));
+      o.v[j] = f4_add(o.v[j], f4_scale(t, rs));
+    }
+    o.store(dx + (size_t)r * C, lane);
+  }
+  ROW_FOR(j, NJ) {
+    const int idx = lane + 64 * j;
+    if (idx < C / 4) {
+      *reinterpret_cast<float4*>(&red[0][wave][4 * idx]) = ag.v[j];
+      *reinterpret_cast<float4*>(&red[1][wave][4 * idx]) = ab.v[j];
+    }
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += 256) {
+    atomic_add_f32(dgamma + c, (red[0][0][c] + red[0][1][c]) + (red[0][2][c] + red[0][3][c]));
+    atomic_add_f32(dbeta + c, (red[1][0][c] + red[1][1][c]) + (red[1][2][c] + red[1][3][c]));
+  }
+}
+
+// ==========================================================================================================
+// GELU (nn.GELU(), exact erf) forward / backward, elementwise over float4
+// ==========================================================================================================
+__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
+__device__ __forceinline__ float gelu_grad_f(float x) {
+  const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752f));
+  const float pdf = 0.3989422804014327f * __expf(-0.5f * x * x);
+  return cdf + x * pdf;
+}
+__global__ __launch_bounds__(256) void s2_gelu_kernel(const float4* __restrict__ h, float4* __restrict__ a, int64_t n4) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  const float4 v = h[i];
+  a[i] = make_float4(gelu_f(v.x), gelu_f(v.y), gelu_f(v.z), gelu_f(v.w));
+}
+__global__ __launch_bounds__(256) void s2_gelu_bwd_kernel(const float4* __restrict__ h, float4* __restrict__ da, int64_t n4) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  const float4 v = h[i], d = da[i];
+  da[i] = make_float4(d.x * gelu_grad_f(v.x), d.y * gelu_grad_f(v.y), d.z * gelu_grad_f(v.z), d.w * gelu_grad_f(v.w));
+}
+
+// ==========================================================================================================
+// Round 6: the two [Tp][Tp]-sized products of a head WITH the softmax arithmetic that used to run over their output.
+// One workgroup = 128 query rows of one (image, head): 4 waves x 32 rows, the row operand (q, or d ao) lives in registers
+// -- 32 fragment values per lane, as in the fp32 extractor's attention kernel --, the key-side operand (k, or v) streams
+// through LDS in 32-key tiles (two buffers, one barrier per tile).  v_mfma_f32_32x32x2_f32 in BOTH operand orders off the
+// SAME registers and the same LDS reads:
+//   T-order  D = K_tile . A^T   lane holds query (lane & 31), keys kappa(r) + 4 (lane >> 5): row statistics are lane-local
+//   N-order  D = A . K_tile^T   lane holds key (lane & 31), queries kappa(r) + 4 (lane >> 5): a half-wave stores 32
+//                               consecutive keys of one query row = one whole 128-B line per instruction
+// MODE 0, forward (main_denoiser.py:138-140 -> timm Attention.forward: softmax(q k^T / 8)): sweep 1 in T-order forms every
+//   query's running max and sum (base 2, the scale folded into q), sweep 2 recomputes the logits in N-order and writes
+//   P = 2^(s - m) / l ONCE.  Before: S written by a 64 x 64-tile GEMM (186 k workgroups of 32 MFMAs per wave), read and
+//   rewritten by s2_softmax_kernel: 9 GB of traffic, 1.76 + 1.22 ms per step at batch 32.  Padded query rows and key columns
+//   (>= T) get P = 0, as s2_softmax_kernel wrote them.
+// MODE 1, backward: dS = scale P (.) (dao v^T - D) in N-order, D = rowsum(dP (.) P) = dao . ao from s2_rowdot_kernel; P is
+//   read once (requested a tile ahead), dP never exists.
+// ==========================================================================================================
+constexpr int AR_Q = 128, AR_K = 32, AR_LD = 65;  // odd pitch: the 32 rows of a key-tile fragment read hit 32 banks
+typedef float floatx16 __attribute__((ext_vector_type(16)));
+
+template <int MODE>
+__global__ __launch_bounds__(256) void s2_attn_rows_kernel(const float* __restrict__ rowop, int ld_row, const float* __restrict__ keyop,
+                                                           int ld_key, const float* __restrict__ Pin, const float* __restrict__ D,
+                                                           float* __restrict__ out, int heads, int T, int Tp, float scale) {
+  __shared__ float Ks[2][AR_K * AR_LD];
+  __shared__ float stat[2][AR_Q];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = lane & 31, h2 = lane >> 5;
+  const int nqb = Tp / AR_Q;
+  const int id = blockIdx.x;
+  const int qb = id % nqb, hd = (id / nqb) % heads, b = id / (nqb * heads);
+  const size_t row0 = (size_t)b * Tp;
+  const int q0w = qb * AR_Q + wave * 32;  // first query row of this wave inside the image
+  const float LOG2E = 1.4426950408889634f;
+  // row-operand fragments of this lane: A[query q0w + j][d = 2 s + h2] (forward: q * scale * log2(e): softmax in base 2)
+  float af[32];
+  {
+    const float* ap = rowop + (row0 + q0w + j) * ld_row + hd * 64 + h2;
+    const float f = MODE == 0 ? scale * LOG2E : 1.0f;
+#pragma unroll
+    for (int s = 0; s < 32; ++s) af[s] = ap[2 * s] * f;
+  }
+  const float* kbase = keyop + row0 * ld_key + hd * 64;
+  float* obase = out + ((size_t)(b * heads + hd) * Tp) * Tp;
+  const float* pbase = MODE == 1 ? Pin + ((size_t)(b * heads + hd) * Tp) * Tp : nullptr;
+  const int ntiles = Tp / AR_K;
+  const int key0 = tid >> 4, dq0 = tid & 15;  // staging: 32 keys x 64 d = 512 float4, two per thread (second: key0 + 16)
+  float4 kr[2];
+  auto fetch = [&](int kt) {
+#pragma unroll
+    for (int it = 0; it < 2; ++it)
+      kr[it] = *reinterpret_cast<const float4*>(kbase + (size_t)(kt * AR_K + key0 + 16 * it) * ld_key + dq0 * 4);
+  };
+  auto park = [&](int buf) {
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      float* kd = Ks[buf] + (key0 + 16 * it) * AR_LD + dq0 * 4;
+      kd[0] = kr[it].x; kd[1] = kr[it].y; kd[2] = kr[it].z; kd[3] = kr[it].w;
+    }
+  };
+  if constexpr (MODE == 0) {
+    // ---- sweep 1 (T-order): running max / sum per query, lane-local over its 16 keys of a tile
+    float m_run = -1e30f, l_run = 0.f;
+    fetch(0);
+    park(0);
+    __syncthreads();
+    for (int kt = 0; kt < ntiles; ++kt) {
+      const int cur = kt & 1;
+      const bool more = kt + 1 < ntiles;
+      if (more) fetch(kt + 1);
+      const float* K = Ks[cur];
+      floatx16 s;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+      for (int t = 0; t < 32; ++t) s = __builtin_amdgcn_mfma_f32_32x32x2f32(K[j * AR_LD + 2 * t + h2], af[t], s, 0, 0, 0);
+      float tmax = -1e30f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = kt * AR_K + (r & 3) + 8 * (r >> 2) + 4 * h2;
+        if (key >= T) s[r] = -1e30f;
+        tmax = fmaxf(tmax, s[r]);
+      }
+      const float m_new = fmaxf(m_run, tmax);
+      float psum = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) psum += __builtin_amdgcn_exp2f(s[r] - m_new);
+      l_run = l_run * __builtin_amdgcn_exp2f(m_run - m_new) + psum;
+      m_run = m_new;
+      if (more) park(cur ^ 1);
+      __syncthreads();
+    }
+    {  // the two lanes of a query (h2 = 0 / 1) hold disjoint keys: merge, then (m, 1 / l) of the wave's 32 queries -> LDS
+      const float m2 = __shfl_xor(m_run, 32, 64), l2 = __shfl_xor(l_run, 32, 64);
+      const float mt = fmaxf(m_run, m2);
+      const float lt = l_run * __builtin_amdgcn_exp2f(m_run - mt) + l2 * __builtin_amdgcn_exp2f(m2 - mt);
+      if (h2 == 0) {
+        stat[0][wave * 32 + j] = mt;
+        stat[1][wave * 32 + j] = 1.0f / lt;
+      }
+    }
+    __syncthreads();
+  }
+  // ---- the N-order sweep: lane = key column (lane & 31), rows kappa(r) + 4 h2 of the wave's 32 queries
+  float rs0[16], rs1[16];  // per row: forward (m, 1 / l); backward (D, -)
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int qi = (r & 3) + 8 * (r >> 2) + 4 * h2;
+    if constexpr (MODE == 0) {
+      rs0[r] = stat[0][wave * 32 + qi];
+      rs1[r] = q0w + qi < T ? stat[1][wave * 32 + qi] : 0.f;  // padded query rows: P = 0
+    } else {
+      rs0[r] = D[(size_t)(b * heads + hd) * Tp + q0w + qi];
+      rs1[r] = scale;
+    }
+  }
+  float pr[16];
+  auto fetch_p = [&](int kt) {
+    if constexpr (MODE == 1) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int qi = (r & 3) + 8 * (r >> 2) + 4 * h2;
+        pr[r] = pbase[(size_t)(q0w + qi) * Tp + kt * AR_K + j];
+      }
+    }
+  };
+  fetch(0);
+  park(0);
+  fetch_p(0);
+  __syncthreads();
+  for (int kt = 0; kt < ntiles; ++kt) {
+    const int cur = kt & 1;
+    const bool more = kt + 1 < ntiles;
+    if (more) fetch(kt + 1);
+    const float* K = Ks[cur];
+    floatx16 s;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+    for (int t = 0; t < 32; ++t) s = __builtin_amdgcn_mfma_f32_32x32x2f32(af[t], K[j * AR_LD + 2 * t + h2], s, 0, 0, 0);
+    const int key = kt * AR_K + j;
+    float o[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      if constexpr (MODE == 0) o[r] = key < T ? __builtin_amdgcn_exp2f(s[r] - rs0[r]) * rs1[r] : 0.f;
+      else o[r] = rs1[r] * pr[r] * (s[r] - rs0[r]);
+    }
+    if (more) fetch_p(kt + 1);  // (behind the uses of this tile's P)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int qi = (r & 3) + 8 * (r >> 2) + 4 * h2;
+      obase[(size_t)(q0w + qi) * Tp + key] = o[r];
+    }
+    if (more) park(cur ^ 1);
+    __syncthreads();
+  }
+}
+
+// D[(b * heads + h) * Tp + t] = sum_d dO[b * Tp + t][64 h + d] * O[b * Tp + t][64 h + d] = rowsum(dP (.) P) of that (image, head, query)
+// (O = P V, dP = dO V^T): what the softmax backward subtracts, from two [R][C] tensors instead of two [.., Tp][Tp] ones.  One
+// wave per token row, 16 lanes per head pass (C / 64 heads, 4 per pass).
+__global__ __launch_bounds__(256) void s2_rowdot_kernel(const float* __restrict__ dO, const float* __restrict__ O,
+                                                        float* __restrict__ D, int R, int Tp, int C) {
+  const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= R) return;
+  const int b = r / Tp, t = r - b * Tp, heads = C >> 6;
+  const float4* a = reinterpret_cast<const float4*>(dO + (size_t)r * C);
+  const float4* o = reinterpret_cast<const float4*>(O + (size_t)r * C);
+  for (int h0 = 0; h0 < heads; h0 += 4) {  // 64 lanes x float4 = 4 heads of 64 columns
+    const int h = h0 + (lane >> 4);
+    float v = h < heads ? f4_dot(a[h0 * 16 + lane], o[h0 * 16 + lane]) : 0.f;
+    v += __shfl_xor(v, 8, 64);
+    v += __shfl_xor(v, 4, 64);
+    v += __shfl_xor(v, 2, 64);
+    v += __shfl_xor(v, 1, 64);
+    if ((lane & 15) == 0 && h < heads) D[((size_t)b * heads + h) * Tp + t] = v;
+  }
+}
+
+template <typename K, typename... A>
+int launch_rows(K kernel, int R, hipStream_t s, A... args) {
+  hipLaunchKernelGGL(kernel, dim3(dvt_cdiv(R, 4)), dim3(256), 0, s, args...);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
+int ln_bwd(int C, const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+           const float* dres, float* dx, float* dgamma, float* dbeta, int R, hipStream_t s) {
+  const dim3 grid(dvt_cdiv(R, 32)), blk(256);
+  switch (C) {
+    case 384: hipLaunchKernelGGL(s2_ln_bwd_kernel<384>, grid, blk, 0, s, dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, R); break;
+    case 768: hipLaunchKernelGGL(s2_ln_bwd_kernel<768>, grid, blk, 0, s, dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, R); break;
+    default: hipLaunchKernelGGL(s2_ln_bwd_kernel<1024>, grid, blk, 0, s, dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, R); break;
+  }
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
+// y[R][n] = x[R][k] . w[n][k]^T + b
+int lin_fwd(const float* x, const float* w, const float* b, float* y, int R, int n, int k, hipStream_t s) {
+  // round 6: the forward linear layers take the fp32 extractor's 128 x 128 x 32 tile where the shape allows (R = batch x 1408
+  // rows, n and k multiples of 128 / 32: every layer of the Block) -- 125 against 97 TF/s; summation order differs only
+  if (g_s2_big_fwd && dvt_linear_big_ok(R, n, k)) return dvt_linear_fwd_big(x, w, b, y, R, n, k, s);
+  DvtGemmEx g{};
+  g.layout = 0;
+  g.A = x; g.B = w; g.C = y;
+  g.M = R; g.N = n; g.K = k;
+  g.lda = k; g.ldb = k; g.ldc = n;
+  g.bias = b;
+  return dvt_gemm_f32_ex(&g, s);
+}
+// side stream + fork / join events of lin_bwd (created once per process, never destroyed; one trainer per process and device)
+hipStream_t g_s2_side = nullptr;
+hipEvent_t g_s2_ev_fork = nullptr, g_s2_ev_join = nullptr;
+bool s2_side_stream(hipStream_t* out) {
+  if (g_s2_side == nullptr) {
+    if (hipStreamCreateWithFlags(&g_s2_side, hipStreamNonBlocking) != hipSuccess) return false;
+    if (hipEventCreateWithFlags(&g_s2_ev_fork, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&g_s2_ev_join, hipEventDisableTiming) != hipSuccess)
+      return false;
+  }
+  *out = g_s2_side;
+  return true;
+}
+
+// out[k][n] = in[n][k] (n, k multiples of 32): 32 x 32 tiles through LDS, both sides in whole 128-B row pieces
+__global__ __launch_bounds__(256) void s2_transpose_kernel(const float* __restrict__ in, float* __restrict__ out, int n, int k) {
+  __shared__ float tile[32][33];
+  const int k0 = blockIdx.x * 32, n0 = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) tile[ty + 8 * i][tx] = in[(size_t)(n0 + ty + 8 * i) * k + k0 + tx];
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) out[(size_t)(k0 + ty + 8 * i) * n + n0 + tx] = tile[tx][ty + 8 * i];
+}
+
+// dx[R][k] = dy[R][n] . w[n][k];  dw[n][k] += dy^T . x;  db[n] += colsum(dy)
+// wT (round 6): scratch for w^T [k][n].  With it the data gradient is a FORWARD linear layer of the transposed weight --
+// dx = dy . (w^T)^T -- and takes the 128 x 128 x 32 tile (dvt_linear_fwd_big: both operands k-contiguous); the transposition is
+// 2 x 9 MB of traffic at most per layer, the GEMM 0.07-0.2 TFLOP.  Summation order differs from the 64 x 64 kernel only.
+int lin_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, float* db, int R, int n, int k,
+            hipStream_t s, float* wT = nullptr) {
+  // Round 6: the weight gradient and the data gradient of a layer are independent products of the same dy.  Their grids are a few
+  // rounds of the chip's 512 workgroup slots each (2112 tiles = 4.1 rounds for the 768-wide outputs: the last round is 1/8
+  // full), so the weight gradient goes to a side stream and the two fill each other's tails; joined before this returns (the
+  // caller's next kernels overwrite dy / x).
+  hipStream_t sw = s;
+  const bool fork = g_s2_fork_wgrad && dx != nullptr && s2_side_stream(&sw);
+  if (fork) {
+    if (hipEventRecord(g_s2_ev_fork, s) != hipSuccess || hipStreamWaitEvent(sw, g_s2_ev_fork, 0) != hipSuccess) return DVT_E_BADARG;
+  } else {
+    sw = s;
+  }
+  if (g_s2_big_wgrad && dvt_linear_wgrad_big_ok(R, n, k)) {  // round 6: the weight gradient on the 128 x 128 tile too
+    S2_TRY(dvt_linear_wgrad_big(dy, x, dw, db, R, n, k, 1, sw));
+  } else {
+    DvtGemmEx g{};
+    g.layout = 2;
+    g.A = dy; g.B = x; g.C = dw;
+    g.M = n; g.N = k; g.K = R;
+    g.lda = n; g.ldb = k; g.ldc = k;
+    g.colsum = db;
+    g.accumulate = 1;
+    S2_TRY(dvt_gemm_f32_ex(&g, sw));
+  }
+  if (!dx) return 0;
+  int rc = 0;
+  if (wT && g_s2_big_bwd && n % 32 == 0 && k % 32 == 0 && dvt_linear_big_ok(R, k, n)) {
+    hipLaunchKernelGGL(s2_transpose_kernel, dim3(k / 32, n / 32), dim3(256), 0, s, w, wT, n, k);
+    DVT_CHECK_LAUNCH();
+    rc = dvt_linear_fwd_big(dy, wT, nullptr, dx, R, k, n, s);
+  } else {
+    DvtGemmEx d{};
+    d.layout = 1;
+    d.A = dy; d.B = w; d.C = dx;
+    d.M = R; d.N = k; d.K = n;
+    d.lda = n; d.ldb = k; d.ldc = k;
+    rc = dvt_gemm_f32_ex(&d, s);
+  }
+  if (fork && (hipEventRecord(g_s2_ev_join, sw) != hipSuccess || hipStreamWaitEvent(s, g_s2_ev_join, 0) != hipSuccess))
+    return DVT_E_BADARG;
+  return rc;
+}
+
+// The six (image, head)-batched attention products.  q/k/v live in qkv [R][3C] at column offsets 0 / C / 2C
+// (+ 64 head), P and dP are [batch*heads][Tp][Tp], per-head outputs are 64-column slices of [R][C] / [R][3C].
+struct AttnDims {
+  int batch, heads, Tp, C;
+};
+DvtGemmEx attn_gemm(const AttnDims& d, int layout, const float* A, int lda, long long sA0, long long sA1, const float* B,
+                    int ldb, long long sB0, long long sB1, float* Cc, int ldc, long long sC0, long long sC1, int M, int N,
+                    int K) {
+  DvtGemmEx g{};
+  g.layout = layout;
+  g.A = A; g.B = B; g.C = Cc;
+  g.M = M; g.N = N; g.K = K;
+  g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+  g.nb0 = d.batch; g.nb1 = d.heads;
+  g.sA0 = sA0; g.sA1 = sA1; g.sB0 = sB0; g.sB1 = sB1; g.sC0 = sC0; g.sC1 = sC1;
+  return g;
+}
+
+}  // namespace

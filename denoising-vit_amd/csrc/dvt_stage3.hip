@@ -1,0 +1,566 @@
+// Stage-3 distillation step (include/dvt_stage3.h): forward, loss and backward of a whole DINOv2 ViT in exact fp32.
+//
+// Reference: main_distillation.py:85-296 (student PretrainedViTWrapper, loss, loop), timm 1.0.7 VisionTransformer
+// (absent third party; forward restated in oracle/vit.py).
+//
+// The block is the stage-2 block (dvt_stage2.hip) with LayerScale: x1 = x + ls1 (.) proj(attn(norm1 x)), x2 = x1 + ls2 (.)
+// fc2(gelu(fc1(norm2 x1))).  Contractions, attention, GELU and the LayerNorm backward are the stage-2 pieces
+// (dvt_s2_parts.h); this file adds the patch embedding (im2col + GEMM, padded weight), the prefix-token / pos_embed assembly,
+// the LayerScale residual add fused with the following LayerNorm (the next block's norm1, or the final norm), the LayerScale
+// backward, the loss over the patch rows, and the assembly's backward.
+//
+// Rows: an image owns s_pad rows (prefix tokens, then patches, then zero padding).  Padded rows are zero in every activation
+// that feeds a reduction over rows, as in stage 2; the prefix rows take part in every block but not in the loss.
+#include "dvt_common.h"
+#include "dvt_s2_parts.h"
+#include "../../include/dvt_stage2.h"
+#include "../../include/dvt_stage3.h"
+
+namespace {
+
+// ==========================================================================================================
+// Patch embedding: im2col of the image (one row per token row; prefix and padded rows zero) and the weight padded from
+// [dim, 3 p p] to [dim, k_patch] (and its gradient back).
+// ==========================================================================================================
+__global__ __launch_bounds__(256) void s3_im2col_kernel(const float* __restrict__ img, float* __restrict__ col, DvtVitConfig c) {
+  const int t = blockIdx.x;  // token row in [0, batch * s_pad)
+  const int b = t / c.s_pad, s = t - b * c.s_pad;
+  float* dst = col + (size_t)t * c.k_patch;
+  const int pp = c.patch * c.patch;
+  if (s < c.n_prefix || s >= c.n_tokens) {
+    for (int k = threadIdx.x; k < c.k_patch; k += 256) dst[k] = 0.f;
+    return;
+  }
+  const int py = (s - c.n_prefix) / c.grid_w, px = (s - c.n_prefix) - py * c.grid_w;
+  const float* src = img + (size_t)b * 3 * c.img_h * c.img_w;
+  for (int k = threadIdx.x; k < c.k_patch; k += 256) {
+    float v = 0.f;
+    if (k < 3 * pp) {
+      const int ch = k / pp, rem = k - ch * pp, ky = rem / c.patch, kx = rem - ky * c.patch;
+      v = src[((size_t)ch * c.img_h + py * c.stride + ky) * c.img_w + px * c.stride + kx];
+    }
+    dst[k] = v;
+  }
+}
+
+// wpad[n][k] = k < k0 ? w[n][k] : 0   (n rows, kp >= k0 columns)
+__global__ __launch_bounds__(256) void s3_pad_kernel(const float* __restrict__ w, float* __restrict__ wpad, int n, int k0, int kp) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)n * kp) return;
+  const int r = (int)(i / kp), k = (int)(i - (int64_t)r * kp);
+  wpad[i] = k < k0 ? w[(int64_t)r * k0 + k] : 0.f;
+}
+
+// g[n][k] += gpad[n][k] for k < k0
+__global__ __launch_bounds__(256) void s3_unpad_add_kernel(const float* __restrict__ gpad, float* __restrict__ g, int n, int k0, int kp) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)n * k0) return;
+  const int r = (int)(i / k0), k = (int)(i - (int64_t)r * k0);
+  g[i] += gpad[(int64_t)r * kp + k];
+}
+
+// x[t] = prefix token (+ pos_embed[0] for cls when the table has a cls row) | patch embedding + pos_embed | 0 (padding)
+// (timm VisionTransformer._pos_embed; oracle/vit.py:forward_features)
+__global__ __launch_bounds__(256) void s3_embed_kernel(const float4* __restrict__ y, float4* __restrict__ x,
+                                                       const float4* __restrict__ prefix, const float4* __restrict__ pos,
+                                                       DvtVitConfig c) {
+  const int t = blockIdx.x, s = t % c.s_pad, dq = c.dim >> 2;
+  for (int q = threadIdx.x; q < dq; q += 256) {
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (s < c.n_prefix) {
+      o = prefix[(size_t)s * dq + q];
+      if (c.pos_has_cls && s == 0) o = f4_add(o, pos[q]);
+    } else if (s < c.n_tokens) {
+      o = f4_add(y[(size_t)t * dq + q], pos[(size_t)(s - c.n_prefix + c.pos_has_cls) * dq + q]);
+    }
+    x[(size_t)t * dq + q] = o;
+  }
+}
+
+// Backward of s3_embed_kernel.  dx [batch * s_pad, dim] (the gradient w.r.t. the first block's input) in, per token row s
+// and float4 column q:  dprefix[s] += sum_b dx[b, s]  (s < n_prefix),  dpos[row of s] += sum_b dx[b, s]  (the cls row when
+// pos_has_cls, every patch row);  then dx's prefix rows are zeroed, so that dx is the patch-embedding output's gradient (its
+// padded rows are zero already).  One thread owns (s, q) over the whole batch: no atomics, no races.
+__global__ __launch_bounds__(256) void s3_embed_bwd_kernel(float4* __restrict__ dx, float4* __restrict__ dprefix,
+                                                           float4* __restrict__ dpos, int batch, DvtVitConfig c) {
+  const int dq = c.dim >> 2;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)c.n_tokens * dq) return;
+  const int s = (int)(i / dq), q = (int)(i - (int64_t)s * dq);
+  float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int b = 0; b < batch; ++b) sum = f4_add(sum, dx[((int64_t)b * c.s_pad + s) * dq + q]);
+  if (s < c.n_prefix) {
+    dprefix[(size_t)s * dq + q] = f4_add(dprefix[(size_t)s * dq + q], sum);
+    if (c.pos_has_cls && s == 0) dpos[q] = f4_add(dpos[q], sum);
+    for (int b = 0; b < batch; ++b) dx[((int64_t)b * c.s_pad + s) * dq + q] = make_float4(0.f, 0.f, 0.f, 0.f);
+  } else {
+    const size_t p = (size_t)(s - c.n_prefix + c.pos_has_cls) * dq + q;
+    dpos[p] = f4_add(dpos[p], sum);
+  }
+}
+
+// ==========================================================================================================
+// LayerScale residual add fused with the LayerNorm behind it, one wave per row (timm Block: x = x + ls(f(norm(x))), then the
+// next block's norm1 or the final norm):  sum = a + ls (.) f,  xn = LayerNorm(sum) * gamma + beta, per-row mean / rstd kept.
+// ls == nullptr: sum = a (the first block's norm1).  Rows t >= T: sum = xn = 0, mean = rstd = 0.  LayerNorm arithmetic as
+// s2_add_ln_kernel (two passes, 1 / sqrt(var + eps)).
+// ==========================================================================================================
+template <int C>
+__global__ __launch_bounds__(256) void s3_ls_add_ln_kernel(const float* __restrict__ a, const float* __restrict__ f,
+                                                           const float* __restrict__ ls, float* __restrict__ sum_out,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           float* __restrict__ xn, float* __restrict__ mean,
+                                                           float* __restrict__ rstd, int T, int Tp, int R, float eps) {
+  const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= R) return;
+  const int t = r % Tp;
+  Row<C> x;
+  if (t >= T) {
+    x.zero();
+    if (sum_out) x.store(sum_out + (size_t)r * C, lane);
+    x.store(xn + (size_t)r * C, lane);
+    if (lane == 0) {
+      mean[r] = 0.f;
+      rstd[r] = 0.f;
+    }
+    return;
+  }
+  x.load(a + (size_t)r * C, lane);
+  if (ls) {
+    Row<C> y, g;
+    y.load(f + (size_t)r * C, lane);
+    g.load(ls, lane);
+    ROW_FOR(j, Row<C>::NJ) x.v[j] = f4_add(x.v[j], f4_mul(g.v[j], y.v[j]));
+  }
+  if (sum_out) x.store(sum_out + (size_t)r * C, lane);
+  const float mu = x.sum() * (1.0f / C);
+  Row<C> d;
+  float ss = 0.f;
+  ROW_FOR(j, Row<C>::NJ) {
+    const int i = lane + 64 * j;
+    d.v[j] = (i < C / 4) ? f4_sub(x.v[j], make_float4(mu, mu, mu, mu)) : make_float4(0.f, 0.f, 0.f, 0.f);
+    ss += f4_dot(d.v[j], d.v[j]);
+  }
+  const float var = wave_sum(ss) * (1.0f / C);
+  const float rs = 1.0f / sqrtf(var + eps);
+  Row<C> g, be;
+  g.load(gamma, lane);
+  be.load(beta, lane);
+  ROW_FOR(j, Row<C>::NJ) d.v[j] = f4_add(f4_mul(f4_scale(d.v[j], rs), g.v[j]), be.v[j]);
+  d.store(xn + (size_t)r * C, lane);
+  if (lane == 0) {
+    mean[r] = mu;
+    rstd[r] = rs;
+  }
+}
+
+// ==========================================================================================================
+// LayerScale backward: y = x + ls (.) f  ->  df = ls (.) dy,  dls += sum_rows f (.) dy  (dx = dy is the caller's residual).
+// A 256-thread block walks 32 rows (8 per wave), reduces the 4 waves through LDS and issues one atomic per column, as
+// s2_ln_bwd_kernel does.
+// ==========================================================================================================
+template <int C>
+__global__ __launch_bounds__(256) void s3_ls_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ f,
+                                                        const float* __restrict__ ls, float* __restrict__ df,
+                                                        float* __restrict__ dls, int R) {
+  constexpr int NJ = Row<C>::NJ;
+  __shared__ float red[4][C];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  Row<C> g, acc;
+  g.load(ls, lane);
+  acc.zero();
+  const int r0 = blockIdx.x * 32 + wave * 8;
+  for (int i = 0; i < 8; ++i) {
+    const int r = r0 + i;
+    if (r >= R) break;
+    Row<C> d, fv;
+    d.load(dy + (size_t)r * C, lane);
+    fv.load(f + (size_t)r * C, lane);
+    ROW_FOR(j, NJ) {
+      acc.v[j] = f4_add(acc.v[j], f4_mul(fv.v[j], d.v[j]));
+      d.v[j] = f4_mul(g.v[j], d.v[j]);
+    }
+    d.store(df + (size_t)r * C, lane);
+  }
+  ROW_FOR(j, NJ) {
+    const int idx = lane + 64 * j;
+    if (idx < C / 4) *reinterpret_cast<float4*>(&red[wave][4 * idx]) = acc.v[j];
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += 256) atomic_add_f32(dls + c, (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]));
+}
+
+// ==========================================================================================================
+// Loss over the patch rows (n_prefix <= t < n_tokens) of the final-normed x, one wave per row (main_distillation.py: mse +
+// 1 - cosine_similarity(dim=-1).mean(), as s2_loss_kernel):  dout = 2 (o - t) / (N C) - (t / (|o| |t|) - cos o / |o|^2) / N
+// with N = norm_batch * patches; acc[0] += sum (o - t)^2, acc[1] += sum cos.  Prefix and padded rows: dout = 0.  The patch
+// rows also go to feat (packed [batch, patches, C]) when it is given.
+// ==========================================================================================================
+template <int C>
+__global__ __launch_bounds__(256) void s3_loss_kernel(const float* __restrict__ xf, const float* __restrict__ target,
+                                                      float* __restrict__ feat, float* __restrict__ dout,
+                                                      float* __restrict__ acc, int n_prefix, int T, int Tp, int R,
+                                                      float inv_el, float inv_tok) {
+  __shared__ float part[2][4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = blockIdx.x * 4 + wave;
+  const int NP = T - n_prefix;
+  float se = 0.f, cs = 0.f;
+  if (r < R) {
+    const int img = r / Tp, t = r - img * Tp;
+    Row<C> o;
+    if (t < n_prefix || t >= T) {
+      o.zero();
+      o.store(dout + (size_t)r * C, lane);
+    } else {
+      const size_t pr = (size_t)img * NP + (t - n_prefix);
+      Row<C> tg;
+      o.load(xf + (size_t)r * C, lane);
+      tg.load(target + pr * C, lane);
+      if (feat) o.store(feat + pr * C, lane);
+      float s_d = 0.f, s_ot = 0.f, s_oo = 0.f, s_tt = 0.f;
+      ROW_FOR(j, Row<C>::NJ) {
+        const float4 d = f4_sub(o.v[j], tg.v[j]);
+        s_d += f4_dot(d, d);
+        s_ot += f4_dot(o.v[j], tg.v[j]);
+        s_oo += f4_dot(o.v[j], o.v[j]);
+        s_tt += f4_dot(tg.v[j], tg.v[j]);
+      }
+      s_d = wave_sum(s_d);
+      s_ot = wave_sum(s_ot);
+      s_oo = wave_sum(s_oo);
+      s_tt = wave_sum(s_tt);
+      const float no = fmaxf(sqrtf(s_oo), 1e-8f), nt = fmaxf(sqrtf(s_tt), 1e-8f);
+      const float cosv = s_ot / (no * nt);
+      const float ka = 2.0f * inv_el, kt = inv_tok / (no * nt), ko = inv_tok * cosv / (no * no);
+      ROW_FOR(j, Row<C>::NJ) {
+        const float4 d = f4_sub(o.v[j], tg.v[j]);
+        float4 g;
+        g.x = ka * d.x - (kt * tg.v[j].x - ko * o.v[j].x);
+        g.y = ka * d.y - (kt * tg.v[j].y - ko * o.v[j].y);
+        g.z = ka * d.z - (kt * tg.v[j].z - ko * o.v[j].z);
+        g.w = ka * d.w - (kt * tg.v[j].w - ko * o.v[j].w);
+        o.v[j] = g;
+      }
+      o.store(dout + (size_t)r * C, lane);
+      se = s_d;
+      cs = cosv;
+    }
+  }
+  if (lane == 0) {
+    part[0][wave] = se;
+    part[1][wave] = cs;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    atomic_add_f32(acc + 0, (part[0][0] + part[0][1]) + (part[0][2] + part[0][3]));
+    atomic_add_f32(acc + 1, (part[1][0] + part[1][1]) + (part[1][2] + part[1][3]));
+  }
+}
+
+// loss_out = {l2 + 1 - cos, l2, 1 - cos, 0} from the two accumulated sums
+__global__ void s3_loss_finish_kernel(const float* __restrict__ acc, float* __restrict__ out, float inv_el, float inv_tok) {
+  if (threadIdx.x != 0) return;
+  const float l2 = acc[0] * inv_el, cl = 1.0f - acc[1] * inv_tok;
+  out[0] = l2 + cl;
+  out[1] = l2;
+  out[2] = cl;
+  out[3] = 0.f;
+}
+
+// ---- host side ------------------------------------------------------------------------------------------
+enum { PATCHW = 0, PATCHB, CLS, REG, POS, BLK0 };
+enum { N1W = 0, N1B, QKVW, QKVB, PROJW, PROJB, LS1, N2W, N2B, FC1W, FC1B, FC2W, FC2B, LS2 };
+
+int check_cfg(const DvtVitConfig* c) {
+  if (!c) return DVT_E_BADARG;
+  if (c->dim != 384 && c->dim != 768 && c->dim != 1024) return DVT_E_BADARG;
+  if (c->heads * 64 != c->dim || c->mlp_dim <= 0 || c->mlp_dim % 128) return DVT_E_BADARG;
+  if (c->depth < 1 || c->depth > DVT_VIT_MAX_DEPTH || c->patch < 1 || c->stride < 1) return DVT_E_BADARG;
+  if (c->grid_h < 1 || c->grid_w < 1 || (c->grid_h - 1) * c->stride + c->patch > c->img_h ||
+      (c->grid_w - 1) * c->stride + c->patch > c->img_w)
+    return DVT_E_BADARG;
+  if (c->n_prefix < 1 || c->n_tokens != c->n_prefix + c->grid_h * c->grid_w) return DVT_E_BADARG;
+  if (c->s_pad < c->n_tokens || c->s_pad % 128) return DVT_E_BADARG;
+  if (c->k_patch < 3 * c->patch * c->patch || c->k_patch % 32) return DVT_E_BADARG;
+  if ((c->pos_has_cls != 0 && c->pos_has_cls != 1) || !(c->ln_eps > 0.f)) return DVT_E_BADARG;
+  return 0;
+}
+
+int64_t n_offsets(const DvtVitConfig* c) { return 8 + (int64_t)DVT_S3_TENSORS_PER_BLOCK * c->depth; }
+
+// out[0 .. n_offsets - 1] as include/dvt_stage3.h lays it out
+void offsets(const DvtVitConfig* c, int64_t* out) {
+  const int64_t C = c->dim, F = c->mlp_dim, pk = 3LL * c->patch * c->patch;
+  int64_t at = 0, i = 0;
+  auto put = [&](int64_t floats) {
+    out[i++] = at;
+    at += (floats + 3) / 4 * 4;  // 16-byte boundaries
+  };
+  put(C * pk);
+  put(C);
+  put(C);
+  put((int64_t)(c->n_prefix - 1) * C);
+  put((int64_t)(c->pos_has_cls + c->grid_h * c->grid_w) * C);
+  const int64_t sz[DVT_S3_TENSORS_PER_BLOCK] = {C, C, 3 * C * C, 3 * C, C * C, C, C, C, C, F * C, F, C * F, C, C};
+  for (int b = 0; b < c->depth; ++b)
+    for (int t = 0; t < DVT_S3_TENSORS_PER_BLOCK; ++t) put(sz[t]);
+  put(C);
+  put(C);
+  out[i] = at;
+}
+
+struct S3Block {  // activations a block keeps for its backward pass
+  float *xin, *xn1, *mean1, *rstd1, *qkv, *P, *ao, *f1, *x1, *xn2, *mean2, *rstd2, *h, *a, *f2;
+};
+struct S3Work {
+  S3Block blk[DVT_VIT_MAX_DEPTH];
+  float *xl, *xf, *meanf, *rstdf;  // the last block's output and its final norm
+  float *col, *wpad, *dwpad, *emb;
+  float *d0, *d1, *d2, *dh, *dqkv, *dP, *acc, *wT, *rowdot;
+};
+
+int64_t carve(const DvtVitConfig* c, int batch, char* base, S3Work* w) {
+  const int64_t R = (int64_t)batch * c->s_pad, C = c->dim, F = c->mlp_dim;
+  const int64_t PP = (int64_t)batch * c->heads * c->s_pad * c->s_pad;
+  int64_t o = 0;
+  auto take = [&](int64_t floats) {
+    float* p = base ? reinterpret_cast<float*>(base + o) : nullptr;
+    o += (floats * 4 + 255) / 256 * 256;
+    return p;
+  };
+  S3Work t{};
+  for (int b = 0; b < c->depth; ++b) {
+    S3Block& k = t.blk[b];
+    k.xin = take(R * C);
+    k.xn1 = take(R * C);
+    k.mean1 = take(R);
+    k.rstd1 = take(R);
+    k.qkv = take(R * 3 * C);
+    k.P = take(PP);
+    k.ao = take(R * C);
+    k.f1 = take(R * C);
+    k.x1 = take(R * C);
+    k.xn2 = take(R * C);
+    k.mean2 = take(R);
+    k.rstd2 = take(R);
+    k.h = take(R * F);
+    k.a = take(R * F);
+    k.f2 = take(R * C);
+  }
+  t.xl = take(R * C);
+  t.xf = take(R * C);
+  t.meanf = take(R);
+  t.rstdf = take(R);
+  t.col = take(R * c->k_patch);
+  t.wpad = take(C * c->k_patch);
+  t.dwpad = take(C * c->k_patch);
+  t.emb = take(R * C);
+  t.d0 = take(R * C);
+  t.d1 = take(R * C);
+  t.d2 = take(R * C);
+  t.dh = take(R * F);
+  t.dqkv = take(R * 3 * C);
+  t.dP = take(PP);
+  t.acc = take(64);
+  t.wT = take((3 * C > F ? 3 * C : F) * C);
+  t.rowdot = take((int64_t)batch * c->heads * c->s_pad);
+  if (w) *w = t;
+  return o;
+}
+
+int ls_add_ln(int C, const float* a, const float* f, const float* ls, float* sum_out, const float* g, const float* be,
+              float* xn, float* mean, float* rstd, int T, int Tp, int R, float eps, hipStream_t s) {
+  switch (C) {
+    case 384: return launch_rows(s3_ls_add_ln_kernel<384>, R, s, a, f, ls, sum_out, g, be, xn, mean, rstd, T, Tp, R, eps);
+    case 768: return launch_rows(s3_ls_add_ln_kernel<768>, R, s, a, f, ls, sum_out, g, be, xn, mean, rstd, T, Tp, R, eps);
+    default: return launch_rows(s3_ls_add_ln_kernel<1024>, R, s, a, f, ls, sum_out, g, be, xn, mean, rstd, T, Tp, R, eps);
+  }
+}
+
+int ls_bwd(int C, const float* dy, const float* f, const float* ls, float* df, float* dls, int R, hipStream_t s) {
+  const dim3 grid(dvt_cdiv(R, 32)), blk(256);
+  switch (C) {
+    case 384: hipLaunchKernelGGL(s3_ls_bwd_kernel<384>, grid, blk, 0, s, dy, f, ls, df, dls, R); break;
+    case 768: hipLaunchKernelGGL(s3_ls_bwd_kernel<768>, grid, blk, 0, s, dy, f, ls, df, dls, R); break;
+    default: hipLaunchKernelGGL(s3_ls_bwd_kernel<1024>, grid, blk, 0, s, dy, f, ls, df, dls, R); break;
+  }
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
+int loss(int C, const float* xf, const float* target, float* feat, float* dout, float* acc, int n_prefix, int T, int Tp, int R,
+         float inv_el, float inv_tok, hipStream_t s) {
+  switch (C) {
+    case 384: return launch_rows(s3_loss_kernel<384>, R, s, xf, target, feat, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok);
+    case 768: return launch_rows(s3_loss_kernel<768>, R, s, xf, target, feat, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok);
+    default: return launch_rows(s3_loss_kernel<1024>, R, s, xf, target, feat, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok);
+  }
+}
+
+int fork_to(hipStream_t s, hipStream_t sv) {
+  if (sv == s) return 0;
+  if (hipEventRecord(g_s2_ev_fork, s) != hipSuccess || hipStreamWaitEvent(sv, g_s2_ev_fork, 0) != hipSuccess) return DVT_E_BADARG;
+  return 0;
+}
+
+int run(const DvtVitConfig* c, const float* params, float* grads, const float* img, const float* target, float* feat,
+        int batch, int norm_batch, void* work, int64_t work_bytes, float* loss_out, hipStream_t s) {
+  S2_TRY(check_cfg(c));
+  if (!params || !grads || !img || !target || !loss_out || !work || batch < 1 || norm_batch < batch) return DVT_E_BADARG;
+  S3Work w;
+  if (carve(c, batch, reinterpret_cast<char*>(work), &w) > work_bytes) return DVT_E_BADARG;
+  int64_t po[8 + DVT_S3_TENSORS_PER_BLOCK * DVT_VIT_MAX_DEPTH];
+  offsets(c, po);
+  const int C = c->dim, F = c->mlp_dim, T = c->n_tokens, Tp = c->s_pad, H = c->heads, NB = c->depth;
+  const int K0 = 3 * c->patch * c->patch, KP = c->k_patch;
+  const int R = batch * Tp;
+  const float scale = 0.125f;  // head_dim^-0.5
+  const AttnDims ad{batch, H, Tp, C};
+  const long long qs0 = (long long)Tp * 3 * C, qs1 = 64, ps0 = (long long)H * Tp * Tp, ps1 = (long long)Tp * Tp,
+                  os0 = (long long)Tp * C, os1 = 64;
+  auto P = [&](int b, int i) { return params + po[BLK0 + DVT_S3_TENSORS_PER_BLOCK * b + i]; };
+  auto G = [&](int b, int i) { return grads + po[BLK0 + DVT_S3_TENSORS_PER_BLOCK * b + i]; };
+  const int64_t normw = po[BLK0 + DVT_S3_TENSORS_PER_BLOCK * NB], normb = po[BLK0 + DVT_S3_TENSORS_PER_BLOCK * NB + 1];
+
+  // ---- forward: patch embedding, token assembly, block 0's norm1 ----
+  {
+    const int64_t n = (int64_t)C * KP;
+    hipLaunchKernelGGL(s3_pad_kernel, dim3(dvt_cdiv(n, 256)), dim3(256), 0, s, params + po[PATCHW], w.wpad, C, K0, KP);
+    DVT_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(s3_im2col_kernel, dim3(R), dim3(256), 0, s, img, w.col, *c);
+  DVT_CHECK_LAUNCH();
+  S2_TRY(lin_fwd(w.col, w.wpad, params + po[PATCHB], w.emb, R, C, KP, s));
+  hipLaunchKernelGGL(s3_embed_kernel, dim3(R), dim3(256), 0, s, (const float4*)w.emb, (float4*)w.blk[0].xin,
+                     (const float4*)(params + po[CLS]), (const float4*)(params + po[POS]), *c);
+  DVT_CHECK_LAUNCH();
+  S2_TRY(ls_add_ln(C, w.blk[0].xin, nullptr, nullptr, nullptr, P(0, N1W), P(0, N1B), w.blk[0].xn1, w.blk[0].mean1,
+                   w.blk[0].rstd1, T, Tp, R, c->ln_eps, s));
+  // ---- the blocks ----
+  for (int b = 0; b < NB; ++b) {
+    const S3Block& k = w.blk[b];
+    S2_TRY(lin_fwd(k.xn1, P(b, QKVW), P(b, QKVB), k.qkv, R, 3 * C, C, s));
+    hipLaunchKernelGGL(s2_attn_rows_kernel<0>, dim3((Tp / AR_Q) * H * batch), dim3(256), 0, s, (const float*)k.qkv, 3 * C,
+                       (const float*)(k.qkv + C), 3 * C, (const float*)nullptr, (const float*)nullptr, k.P, H, T, Tp, scale);
+    DVT_CHECK_LAUNCH();
+    DvtGemmEx g = attn_gemm(ad, 1, k.P, Tp, ps0, ps1, k.qkv + 2 * C, 3 * C, qs0, qs1, k.ao, C, os0, os1, Tp, 64, Tp);
+    S2_TRY(dvt_gemm_f32_ex(&g, s));
+    S2_TRY(lin_fwd(k.ao, P(b, PROJW), P(b, PROJB), k.f1, R, C, C, s));
+    S2_TRY(ls_add_ln(C, k.xin, k.f1, P(b, LS1), k.x1, P(b, N2W), P(b, N2B), k.xn2, k.mean2, k.rstd2, T, Tp, R, c->ln_eps, s));
+    S2_TRY(lin_fwd(k.xn2, P(b, FC1W), P(b, FC1B), k.h, R, F, C, s));
+    {
+      const int64_t n4 = (int64_t)R * F / 4;
+      hipLaunchKernelGGL(s2_gelu_kernel, dim3(dvt_cdiv(n4, 256)), dim3(256), 0, s, (const float4*)k.h, (float4*)k.a, n4);
+      DVT_CHECK_LAUNCH();
+    }
+    S2_TRY(lin_fwd(k.a, P(b, FC2W), P(b, FC2B), k.f2, R, C, F, s));
+    if (b + 1 < NB) {
+      const S3Block& n = w.blk[b + 1];
+      S2_TRY(ls_add_ln(C, k.x1, k.f2, P(b, LS2), n.xin, P(b + 1, N1W), P(b + 1, N1B), n.xn1, n.mean1, n.rstd1, T, Tp, R,
+                       c->ln_eps, s));
+    } else {
+      S2_TRY(ls_add_ln(C, k.x1, k.f2, P(b, LS2), w.xl, params + normw, params + normb, w.xf, w.meanf, w.rstdf, T, Tp, R,
+                       c->ln_eps, s));
+    }
+  }
+
+  // ---- loss over the patch rows ----
+  const float NP = (float)(T - c->n_prefix);
+  const float inv_el = 1.0f / ((float)norm_batch * NP * C), inv_tok = 1.0f / ((float)norm_batch * NP);
+  {
+    const hipError_t e = hipMemsetAsync(w.acc, 0, 64 * sizeof(float), s);
+    if (e != hipSuccess) return (int)e;
+  }
+  S2_TRY(loss(C, w.xf, target, feat, w.d1, w.acc, c->n_prefix, T, Tp, R, inv_el, inv_tok, s));
+  hipLaunchKernelGGL(s3_loss_finish_kernel, dim3(1), dim3(64), 0, s, (const float*)w.acc, loss_out, inv_el, inv_tok);
+  DVT_CHECK_LAUNCH();
+  // final norm: d0 = d xl
+  S2_TRY(ln_bwd(C, w.d1, w.xl, w.meanf, w.rstdf, params + normw, nullptr, w.d0, grads + normw, grads + normb, R, s));
+
+  // ---- backward: d0 holds the gradient w.r.t. the current block's OUTPUT ----
+  for (int b = NB - 1; b >= 0; --b) {
+    const S3Block& k = w.blk[b];
+    // mlp: out = x1 + ls2 (.) fc2(gelu(fc1(norm2(x1))))
+    S2_TRY(ls_bwd(C, w.d0, k.f2, P(b, LS2), w.d1, G(b, LS2), R, s));  // d1 = d f2
+    S2_TRY(lin_bwd(w.d1, k.a, P(b, FC2W), w.dh, G(b, FC2W), G(b, FC2B), R, C, F, s, w.wT));
+    {
+      const int64_t n4 = (int64_t)R * F / 4;
+      hipLaunchKernelGGL(s2_gelu_bwd_kernel, dim3(dvt_cdiv(n4, 256)), dim3(256), 0, s, (const float4*)k.h, (float4*)w.dh, n4);
+      DVT_CHECK_LAUNCH();
+    }
+    S2_TRY(lin_bwd(w.dh, k.xn2, P(b, FC1W), w.d2, G(b, FC1W), G(b, FC1B), R, F, C, s, w.wT));
+    S2_TRY(ln_bwd(C, w.d2, k.x1, k.mean2, k.rstd2, P(b, N2W), w.d0, w.d1, G(b, N2W), G(b, N2B), R, s));  // d1 = d x1
+    // attention: x1 = xin + ls1 (.) proj(attn(norm1(xin)))
+    S2_TRY(ls_bwd(C, w.d1, k.f1, P(b, LS1), w.d0, G(b, LS1), R, s));  // d0 = d f1
+    S2_TRY(lin_bwd(w.d0, k.ao, P(b, PROJW), w.d2, G(b, PROJW), G(b, PROJB), R, C, C, s, w.wT));  // d2 = d ao
+    {
+      // as the stage-2 step: dV = P^T dao on the side stream beside the dS chain, dS = scale P (.) (dao v^T - rowsum) in the
+      // attention-row kernel, then dq = dS k here and dk = dS^T q on the side stream; joined before lin_bwd reads dqkv
+      hipStream_t sv = s;
+      const bool fork = g_s2_fork_wgrad && s2_side_stream(&sv);
+      if (!fork) sv = s;
+      S2_TRY(fork_to(s, sv));
+      DvtGemmEx g = attn_gemm(ad, 2, k.P, Tp, ps0, ps1, w.d2, C, os0, os1, w.dqkv + 2 * C, 3 * C, qs0, qs1, Tp, 64, Tp);
+      S2_TRY(dvt_gemm_f32_ex(&g, sv));
+      hipLaunchKernelGGL(s2_rowdot_kernel, dim3(dvt_cdiv(R, 4)), dim3(256), 0, s, (const float*)w.d2, (const float*)k.ao, w.rowdot, R, Tp, C);
+      DVT_CHECK_LAUNCH();
+      hipLaunchKernelGGL(s2_attn_rows_kernel<1>, dim3((Tp / AR_Q) * H * batch), dim3(256), 0, s, (const float*)w.d2, C,
+                         (const float*)(k.qkv + 2 * C), 3 * C, (const float*)k.P, (const float*)w.rowdot, w.dP, H, T, Tp, scale);
+      DVT_CHECK_LAUNCH();
+      S2_TRY(fork_to(s, sv));
+      g = attn_gemm(ad, 1, w.dP, Tp, ps0, ps1, k.qkv + C, 3 * C, qs0, qs1, w.dqkv, 3 * C, qs0, qs1, Tp, 64, Tp);
+      S2_TRY(dvt_gemm_f32_ex(&g, s));
+      g = attn_gemm(ad, 2, w.dP, Tp, ps0, ps1, k.qkv, 3 * C, qs0, qs1, w.dqkv + C, 3 * C, qs0, qs1, Tp, 64, Tp);
+      S2_TRY(dvt_gemm_f32_ex(&g, sv));
+      if (fork && (hipEventRecord(g_s2_ev_join, sv) != hipSuccess || hipStreamWaitEvent(s, g_s2_ev_join, 0) != hipSuccess))
+        return DVT_E_BADARG;
+    }
+    S2_TRY(lin_bwd(w.dqkv, k.xn1, P(b, QKVW), w.d2, G(b, QKVW), G(b, QKVB), R, 3 * C, C, s, w.wT));
+    S2_TRY(ln_bwd(C, w.d2, k.xin, k.mean1, k.rstd1, P(b, N1W), w.d1, w.d0, G(b, N1W), G(b, N1B), R, s));  // d0 = d xin
+  }
+  // ---- token assembly and patch embedding ----
+  {
+    const int64_t n = (int64_t)T * (C / 4);
+    hipLaunchKernelGGL(s3_embed_bwd_kernel, dim3(dvt_cdiv(n, 256)), dim3(256), 0, s, (float4*)w.d0, (float4*)(grads + po[CLS]),
+                       (float4*)(grads + po[POS]), batch, *c);
+    DVT_CHECK_LAUNCH();
+  }
+  {
+    const hipError_t e = hipMemsetAsync(w.dwpad, 0, sizeof(float) * (size_t)C * KP, s);
+    if (e != hipSuccess) return (int)e;
+  }
+  S2_TRY(lin_bwd(w.d0, w.col, w.wpad, nullptr, w.dwpad, grads + po[PATCHB], R, C, KP, s));
+  {
+    const int64_t n = (int64_t)C * K0;
+    hipLaunchKernelGGL(s3_unpad_add_kernel, dim3(dvt_cdiv(n, 256)), dim3(256), 0, s, (const float*)w.dwpad, grads + po[PATCHW],
+                       C, K0, KP);
+    DVT_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int dvt_s3_param_offsets(const DvtVitConfig* cfg, int64_t* out) {
+  if (!out) return DVT_E_BADARG;
+  S2_TRY(check_cfg(cfg));
+  offsets(cfg, out);
+  return 0;
+}
+
+extern "C" int64_t dvt_s3_workspace_bytes(const DvtVitConfig* cfg, int batch) {
+  if (check_cfg(cfg) != 0 || batch < 1) return -1;
+  return carve(cfg, batch, nullptr, nullptr);
+}
+
+extern "C" int dvt_s3_train_slice(const DvtVitConfig* cfg, const float* params, float* grads, const float* img,
+                                  const float* target, float* feat_out, int batch, int norm_batch, void* work,
+                                  int64_t work_bytes, float* loss_out, void* stream) {
+  return run(cfg, params, grads, img, target, feat_out, batch, norm_batch, work, work_bytes, loss_out, (hipStream_t)stream);
+}
+
+extern "C" int dvt_s3_train_step(const DvtVitConfig* cfg, const float* params, float* grads, const float* img,
+                                 const float* target, float* feat_out, int batch, void* work, int64_t work_bytes,
+                                 float* loss_out, void* stream) {
+  return run(cfg, params, grads, img, target, feat_out, batch, batch, work, work_bytes, loss_out, (hipStream_t)stream);
+}

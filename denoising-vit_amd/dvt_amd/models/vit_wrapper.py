@@ -142,6 +142,9 @@ class PretrainedViTWrapper(nn.Module):
         if path:
             sd = torch.load(path, map_location="cpu")
             sd = sd.get("state_dict", sd.get("model", sd))
+            # a stage-3 checkpoint holds the wrapper's state_dict: every key is `model.<timm key>`
+            if sd and all(k.startswith("model.") for k in sd):
+                sd = {k[len("model."):]: v for k, v in sd.items()}
         elif not self.allow_random_init:
             raise RuntimeError(
                 f"{model_identifier}: no pretrained checkpoint (timm cannot download here). Pass "

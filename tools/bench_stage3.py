@@ -1,0 +1,71 @@
+"""Time the stage-3 student step (csrc/dvt_stage3.hip): forward + loss + backward + AdamW of a whole ViT in fp32.
+
+Prints one JSON line: ms per step, images/s, and the step's matrix FLOPs per second against the 157 TF/s fp32 MFMA peak
+of the MI355X.  The FLOPs count the student only (forward 1x, backward 2x; tokens padded to s_pad rows as the kernels
+run them, attention over all s_pad keys); the teacher's forward (fp32 ViT + the denoiser block, about 1/3 of the
+student's step) is not part of the timed step.
+
+    python tools/bench_stage3.py [--dim 768 --depth 12 --img 518 --batch 64 --steps 3 --warmup 1]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "denoising-vit_amd"))
+
+import torch  # noqa: E402
+
+from dvt_amd import s3  # noqa: E402
+from dvt_amd.vit import random_state_dict  # noqa: E402
+
+PEAK_FP32 = 157e12
+
+
+def step_flops(cfg, batch):
+    R, C, F, Tp = batch * cfg.s_pad, cfg.dim, cfg.mlp_dim, cfg.s_pad
+    patch = 2 * R * C * cfg.k_patch
+    block = 2 * R * C * (3 * C + C + 2 * F) + 2 * 2 * batch * cfg.heads * Tp * Tp * 64
+    return 3 * (patch + cfg.depth * block) - 2 * R * C * cfg.k_patch  # no data gradient for the image
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--dim", type=int, default=768)
+    p.add_argument("--depth", type=int, default=12)
+    p.add_argument("--img", type=int, default=518)
+    p.add_argument("--batch", type=int, default=64)
+    p.add_argument("--micro_batch", type=int, default=0)
+    p.add_argument("--steps", type=int, default=3)
+    p.add_argument("--warmup", type=int, default=1)
+    a = p.parse_args()
+    dev = torch.device("cuda:0")
+    cfg = s3.make_config(a.dim, a.depth, 14, 14, a.img, a.img)
+    eng = s3.Stage3Engine(cfg, dev)
+    eng.load_timm(random_state_dict(a.dim, a.depth, 14, 1 + cfg.grid_h * cfg.grid_w, well_conditioned=True))
+    g = torch.Generator(device=dev).manual_seed(0)
+    img = torch.randn(a.batch, 3, a.img, a.img, device=dev, generator=g)
+    tgt = torch.randn(a.batch, cfg.grid_h, cfg.grid_w, a.dim, device=dev, generator=g)
+    mb = a.micro_batch or None
+    for _ in range(a.warmup):
+        eng.train_step(img, tgt, micro_batch=mb)
+        eng.adamw_step(1e-5, 1e-5)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(a.steps):
+        loss = eng.train_step(img, tgt, micro_batch=mb)
+        eng.adamw_step(1e-5, 1e-5)
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / a.steps
+    fl = step_flops(cfg, a.batch)
+    print(json.dumps({"bench": "stage3_student_step", "dim": a.dim, "depth": a.depth, "img": a.img, "batch": a.batch,
+                      "slice": eng.slice_size(a.batch) if mb is None else mb, "ms_per_step": round(dt * 1e3, 2),
+                      "images_per_s": round(a.batch / dt, 3), "tflop_per_step": round(fl / 1e12, 2),
+                      "tflops": round(fl / dt / 1e12, 2), "fraction_of_fp32_peak": round(fl / dt / PEAK_FP32, 3),
+                      "loss": float(loss[0].cpu())}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
