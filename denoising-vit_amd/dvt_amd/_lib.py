@@ -27,6 +27,7 @@ HIP_SOURCES = [
     "dvt_vit_f32.hip",
     "dvt_stage2.hip",
     "dvt_stage3.hip",
+    "dvt_seg.hip",
     "dvt_prof.hip",
     "dvt_views.hip",
 ]
