@@ -3005,3 +3005,18 @@ extern "C" int dvt_vit_forward(const DvtVitConfig* c, const DvtVitWeights* w, co
   DVT_CHECK_LAUNCH();
   return 0;
 }
+
+// The forward plus the final-normed cls row of every image: cls [batch, dim] fp32.  The patch tokens are the plain
+// forward's; the cls rows come from the same residual stream (row b * s_pad of the workspace) through the same kernel.
+extern "C" int dvt_vit_forward_cls(const DvtVitConfig* c, const DvtVitWeights* w, const float* img, float* feat,
+                                   float* cls, int batch, int n_blocks, void* workspace, void* stream) {
+  if (!cls) return DVT_E_BADARG;
+  const int rc = dvt_vit_forward(c, w, img, feat, batch, n_blocks, workspace, stream);
+  if (rc) return rc;
+  VitWork k;
+  vit_carve(c, batch, (char*)workspace, &k);
+  hipLaunchKernelGGL(layernorm_kernel<true>, dim3(dvt_cdiv(batch, 4)), dim3(256), 0, (hipStream_t)stream, k.x, w->norm_w,
+                     w->norm_b, (bf16_t*)nullptr, cls, batch, c->dim, c->ln_eps, c->s_pad, 1, 0);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}

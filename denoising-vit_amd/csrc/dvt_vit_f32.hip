@@ -582,3 +582,31 @@ extern "C" int dvt_vit_forward_f32(const DvtVitConfig* c, const DvtVitWeights* w
   DVT_CHECK_LAUNCH();
   return 0;
 }
+
+// dvt_vit_forward_f32 plus the final-normed cls row of every image (cls [batch, dim] fp32), read from the same residual stream.
+extern "C" int dvt_vit_forward_f32_cls(const DvtVitConfig* c, const DvtVitWeights* w, const float* img, float* feat, float* cls,
+                          int batch, int n_blocks, void* workspace, void* stream) {
+  if (!cls) return DVT_E_BADARG;
+  const int rc = dvt_vit_forward_f32(c, w, img, feat, batch, n_blocks, workspace, stream);
+  if (rc) return rc;
+  VitWorkF k;
+  carve_f32(c, batch, (char*)workspace, &k);
+  hipLaunchKernelGGL(layernorm_f32_kernel<true>, dim3(dvt_cdiv(batch, 4)), dim3(256), 0, (hipStream_t)stream, k.x, w->norm_w,
+                     w->norm_b, cls, batch, c->dim, c->ln_eps, c->s_pad, 1, 0);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
+// dvt_vit_forward_f32x3 plus the final-normed cls row of every image (cls [batch, dim] fp32), read from the same residual stream.
+extern "C" int dvt_vit_forward_f32x3_cls(const DvtVitConfig* c, const DvtVitWeights* w, const float* img, float* feat, float* cls,
+                          int batch, int n_blocks, void* workspace, void* stream) {
+  if (!cls) return DVT_E_BADARG;
+  const int rc = dvt_vit_forward_f32x3(c, w, img, feat, batch, n_blocks, workspace, stream);
+  if (rc) return rc;
+  VitWorkX3 k;
+  carve_x3(c, batch, (char*)workspace, &k);
+  hipLaunchKernelGGL(layernorm_f32_kernel<true>, dim3(dvt_cdiv(batch, 4)), dim3(256), 0, (hipStream_t)stream, k.x, w->norm_w,
+                     w->norm_b, cls, batch, c->dim, c->ln_eps, c->s_pad, 1, 0);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}

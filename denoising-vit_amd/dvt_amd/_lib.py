@@ -28,6 +28,7 @@ HIP_SOURCES = [
     "dvt_stage2.hip",
     "dvt_stage3.hip",
     "dvt_seg.hip",
+    "dvt_depth.hip",
     "dvt_prof.hip",
     "dvt_views.hip",
 ]

@@ -12,6 +12,11 @@ statistics records, one flat gradient all-reduce per step, evaluation histograms
 
 Outputs in --work-dir: iter_{n}.pth / latest.pth (mmcv layout: meta, state_dict, optimizer), a log with mmseg's per-class
 table, and eval_results.json.
+
+`--task depth` with the `nyu_linear` preset (or a reference-style depth config file) is the reference's NYU Depth v2 linear
+probe: the depth BNHead on csrc/dvt_depth.hip (dvt_amd.depth) over the patch tokens and the cls token, the data pipeline of
+dvt_amd.depth_data, flip-averaged whole-image inference and the nine metrics; besides the files above it keeps the newest
+two iter_{n}.pth and best_abs_rel_iter_{n}.pth.  A task that does not match the config's kind is refused.
 """
 from __future__ import annotations
 
@@ -27,6 +32,8 @@ import time
 import numpy as np
 import torch
 
+from . import depth as DP
+from . import depth_data as DD
 from . import seg as S
 from . import seg_data as D
 
@@ -64,6 +71,41 @@ PRESETS = {
     "ade20k_linear": _common("ADE20KDataset", "data/ADEChallengeData2016", 150,
                              {"img_dir": "images/training", "ann_dir": "annotations/training"},
                              {"img_dir": "images/validation", "ann_dir": "annotations/validation"}),
+}
+
+
+def _nyu_part(split):
+    return {"type": "NYUDataset", "data_root": "data/nyu", "depth_scale": 1000, "split": split, "garg_crop": False,
+            "eigen_crop": True, "min_depth": 0.001, "max_depth": 10}
+
+
+# the values of the reference's vitb_nyu_linear_config.py that the port reads
+DEPTH_PRESETS = {
+    "nyu_linear": {
+        "dataset_type": "NYUDataset",
+        "data": {"samples_per_gpu": 2, "workers_per_gpu": 2, "train": _nyu_part("nyu_train.txt"), "val": _nyu_part("nyu_test.txt")},
+        "crop_size": (416, 544),
+        "optimizer": {"type": "AdamW", "lr": 0.005, "betas": (0.9, 0.999), "weight_decay": 0.01},
+        "lr_config": {"policy": "CosineAnnealing", "warmup": "linear", "warmup_iters": 12800, "warmup_ratio": 0.001,
+                      "min_lr_ratio": 1e-8, "by_epoch": False},
+        "momentum_config": {"policy": "OneCycle"},
+        "optimizer_config": {"grad_clip": {"max_norm": 35, "norm_type": 2}},
+        "runner": {"type": "IterBasedRunner", "max_iters": 38400},
+        "checkpoint_config": {"by_epoch": False, "max_keep_ckpts": 2, "interval": 1600},
+        "evaluation": {"by_epoch": False, "interval": 800, "pre_eval": True, "rule": "less", "save_best": "abs_rel"},
+        "log_config": {"interval": 50},
+        "model": {"type": "DepthEncoderDecoder",
+                  "backbone": {"final_norm": True, "with_cls_token": True, "output_cls_token": True, "out_indices": [11]},
+                  "decode_head": {"type": "BNHead", "norm_cfg": None, "min_depth": 0.001, "max_depth": 10,
+                                  "loss_decode": [{"type": "SigLoss", "valid_mask": True, "loss_weight": 1.0, "warm_up": True,
+                                                   "loss_name": "loss_depth"},
+                                                  {"type": "GradientLoss", "valid_mask": True, "loss_weight": 0.5,
+                                                   "loss_name": "loss_grad"}],
+                                  "classify": True, "n_bins": 256, "bins_strategy": "UD", "norm_strategy": "linear",
+                                  "upsample": 4, "in_index": [0], "input_transform": "resize_concat", "align_corners": False},
+                  "test_cfg": {"mode": "whole"}},
+        "work_dir": None,
+    },
 }
 
 
@@ -139,6 +181,106 @@ def from_file(path: str) -> dict:
     return cfg
 
 
+def from_file_depth(path: str) -> dict:
+    raw = load_config_file(path)
+    cfg = copy.deepcopy(DEPTH_PRESETS["nyu_linear"])
+    data = raw.get("data", {})
+    for part in ("train", "val"):
+        if part in data:
+            cfg["data"][part] = {k: v for k, v in data[part].items() if k != "pipeline"}
+    for k in ("samples_per_gpu", "workers_per_gpu"):
+        if k in data:
+            cfg["data"][k] = data[k]
+    for k in ("dataset_type", "optimizer", "lr_config", "momentum_config", "optimizer_config", "runner", "checkpoint_config",
+              "evaluation", "log_config", "work_dir"):
+        if k in raw:
+            cfg[k] = raw[k]
+    cfg["optimizer"] = {k: v for k, v in cfg["optimizer"].items() if k != "paramwise_cfg"}  # no key of it matches the head
+    m = raw.get("model", {})
+    cfg["model"] = {"type": m.get("type"), "backbone": m.get("backbone", {}), "decode_head": m.get("decode_head", {}),
+                    "test_cfg": m.get("test_cfg", {})}
+    cfg["model"]["backbone"].pop("type", None)
+    for p in data.get("train", {}).get("pipeline", []):
+        if p.get("type") == "RandomCrop":
+            cfg["crop_size"] = tuple(p["crop_size"])
+    return cfg
+
+
+def config_kind(config: str) -> str:
+    """"depth" or "segmentation": what a preset or a config file describes."""
+    if config in DEPTH_PRESETS:
+        return "depth"
+    if config in PRESETS or not os.path.exists(config):
+        return "segmentation"
+    raw = load_config_file(config)
+    depth = raw.get("model", {}).get("type") == "DepthEncoderDecoder" or raw.get("dataset_type") in ("NYUDataset", "KITTIDataset")
+    return "depth" if depth else "segmentation"
+
+
+def validate_depth(cfg: dict) -> None:
+    """Refuse what the depth port does not implement, naming the value."""
+    def need(cond, what):
+        if not cond:
+            raise NotImplementedError(f"not supported by this port: {what}")
+    m = cfg["model"]
+    head = m.get("decode_head", {})
+    need(m.get("type", "DepthEncoderDecoder") == "DepthEncoderDecoder", f"model.type={m.get('type')}")
+    need(head.get("type", "BNHead") == "BNHead", f"model.decode_head.type={head.get('type')}")
+    need(head.get("norm_cfg") is None, f"model.decode_head.norm_cfg={head.get('norm_cfg')}")
+    need(head.get("classify", True), "model.decode_head.classify=False")
+    need(head.get("bins_strategy", "UD") == "UD", f"model.decode_head.bins_strategy={head.get('bins_strategy')}")
+    need(head.get("norm_strategy", "linear") == "linear", f"model.decode_head.norm_strategy={head.get('norm_strategy')}")
+    need(not head.get("scale_up", False), "model.decode_head.scale_up=True")
+    need(head.get("input_transform", "resize_concat") == "resize_concat",
+         f"model.decode_head.input_transform={head.get('input_transform')}")
+    need(len(head.get("in_index", [0])) == 1, f"model.decode_head.in_index={head.get('in_index')} (one layer only)")
+    need(len(m.get("backbone", {}).get("out_indices", [11])) == 1,
+         f"model.backbone.out_indices={m.get('backbone', {}).get('out_indices')} (the last block only)")
+    need(m.get("backbone", {}).get("final_norm", True) and m.get("backbone", {}).get("output_cls_token", True),
+         "model.backbone without final_norm / output_cls_token")
+    need(not head.get("align_corners", False), "model.decode_head.align_corners=True")
+    need(1 <= int(head.get("upsample", 4)) <= 8, f"model.decode_head.upsample={head.get('upsample')}")
+    nb = head.get("n_bins", 256)
+    need(isinstance(nb, int) and 4 <= nb <= 256 and nb % 4 == 0, f"model.decode_head.n_bins={nb}")
+    losses = head.get("loss_decode", [])
+    losses = losses if isinstance(losses, (list, tuple)) else [losses]
+    ok = (len(losses) == 2 and losses[0].get("type") == "SigLoss" and losses[0].get("valid_mask", True)
+          and losses[0].get("warm_up", False) and losses[0].get("loss_weight", 1.0) == 1.0
+          and losses[0].get("warm_iter", 100) == 100 and losses[0].get("max_depth") is None
+          and losses[1].get("type") == "GradientLoss" and losses[1].get("valid_mask", True)
+          and losses[1].get("max_depth") is None)
+    need(ok, f"model.decode_head.loss_decode={losses}")
+    need(m.get("test_cfg", {}).get("mode", "whole") == "whole", f"model.test_cfg.mode={m.get('test_cfg', {}).get('mode')}")
+    for part in ("train", "val"):
+        d = cfg["data"][part]
+        need(d.get("type") == "NYUDataset", f"data.{part}.type={d.get('type')}")
+        need(not d.get("garg_crop", False), f"data.{part}.garg_crop=True")
+        need(d.get("split"), f"data.{part}.split={d.get('split')}")
+    opt = cfg["optimizer"]
+    need(opt.get("type") == "AdamW", f"optimizer.type={opt.get('type')}")
+    lr = cfg["lr_config"]
+    need(lr.get("policy") == "CosineAnnealing", f"lr_config.policy={lr.get('policy')}")
+    need(lr.get("warmup") in ("linear", None), f"lr_config.warmup={lr.get('warmup')}")
+    need(not lr.get("by_epoch", False), "lr_config.by_epoch=True")
+    mom = cfg.get("momentum_config")
+    need(mom is None or mom.get("policy") == "OneCycle", f"momentum_config.policy={(mom or {}).get('policy')}")
+    clip = (cfg.get("optimizer_config") or {}).get("grad_clip")
+    need(clip is None or clip.get("norm_type", 2) == 2, f"optimizer_config.grad_clip.norm_type={(clip or {}).get('norm_type')}")
+    need(cfg["runner"].get("type", "IterBasedRunner") == "IterBasedRunner", f"runner.type={cfg['runner'].get('type')}")
+    ev = cfg.get("evaluation", {})
+    need(ev.get("save_best", "abs_rel") in DP.METRICS + (None,), f"evaluation.save_best={ev.get('save_best')}")
+
+
+def build_depth_config(config: str, cfg_options=None, data_root: str | None = None) -> dict:
+    cfg = copy.deepcopy(DEPTH_PRESETS[config]) if config in DEPTH_PRESETS else from_file_depth(config)
+    apply_cfg_options(cfg, cfg_options)
+    if data_root:
+        for part in ("train", "val"):
+            cfg["data"][part]["data_root"] = data_root
+    validate_depth(cfg)
+    return cfg
+
+
 def parse_value(s: str):
     """mmcv DictAction: ints, floats, booleans, None, lists / tuples (`[a,b]`, `(a,b)`, `a,b`), else a string."""
     try:
@@ -160,7 +302,9 @@ def apply_cfg_options(cfg: dict, options) -> None:
         node = cfg
         parts = key.split(".")
         for p in parts[:-1]:
-            node = node.setdefault(p, {})
+            if not isinstance(node.get(p), dict):  # a None or scalar on the way is replaced, as mmcv's merge does
+                node[p] = {}
+            node = node[p]
         node[parts[-1]] = parse_value(val)
 
 
@@ -211,7 +355,8 @@ def build_config(config: str, cfg_options=None, data_root: str | None = None) ->
 
 def get_args(argv=None):
     p = argparse.ArgumentParser("Linear Evaluation (HIP)")
-    p.add_argument("config", help="preset (voc2012_linear, ade20k_linear) or a reference-style config file")
+    p.add_argument("config", help="preset (voc2012_linear, ade20k_linear; nyu_linear with --task depth) or a reference-style "
+                                  "config file")
     p.add_argument("--work-dir")
     p.add_argument("--load-denoiser-from")
     p.add_argument("--load-distilled-model-from")
@@ -234,8 +379,9 @@ def get_args(argv=None):
     p.add_argument("--dtype", default="bfloat16", choices=["float32", "bfloat16"], help="extractor arithmetic")
     p.add_argument("--data-root", help="overrides data.train / data.val data_root")
     a = p.parse_args(argv)
-    if a.task != "segmentation":
-        p.error(f"--task {a.task} is not built: only the segmentation linear probe is ported (depth stays out of scope)")
+    kind = config_kind(a.config)
+    if kind != a.task:
+        p.error(f"{a.config} is a {kind} config, not a {a.task} one: pass --task {kind}")
     if a.launcher in ("slurm", "mpi"):
         p.error(f"--launcher {a.launcher} is not supported: use --launcher pytorch (torchrun) or none")
     return a
@@ -322,6 +468,8 @@ def metrics_table(met: dict, classes) -> str:
 # ================================================================================================ training
 def main(argv=None) -> dict:
     args = get_args(argv)
+    if args.task == "depth":
+        return main_depth(args)
     opts = (args.cfg_options or []) + (args.options or [])
     cfg = build_config(args.config, opts, args.data_root)
     work_dir = args.work_dir or cfg.get("work_dir") or os.path.join(
@@ -422,6 +570,182 @@ def main(argv=None) -> dict:
     finally:
         feeder.close()
     return {"work_dir": work_dir, "results": results}
+
+
+# ================================================================================================ depth
+def depth_optimizer_state(head, opt_cfg: dict, lr: float, beta1: float) -> dict:
+    """torch.optim.AdamW's state_dict layout over conv_depth.weight and conv_depth.bias."""
+    names = ["conv_depth.weight", "conv_depth.bias"]
+    m, v = head.views(head.exp_avg), head.views(head.exp_avg_sq)
+    state = {i: {"step": torch.tensor(float(head.step)), "exp_avg": m[n].detach().cpu().clone(),
+                 "exp_avg_sq": v[n].detach().cpu().clone()} for i, n in enumerate(names)} if head.step else {}
+    group = {"lr": lr, "betas": (beta1, tuple(opt_cfg.get("betas", (0.9, 0.999)))[1]), "eps": 1e-8,
+             "weight_decay": opt_cfg.get("weight_decay", 0.01), "amsgrad": False, "initial_lr": opt_cfg["lr"], "params": [0, 1]}
+    return {"state": state, "param_groups": [group]}
+
+
+def load_depth_optimizer_state(head, st: dict) -> None:
+    m, v = head.views(head.exp_avg), head.views(head.exp_avg_sq)
+    for i, n in enumerate(["conv_depth.weight", "conv_depth.bias"]):
+        s = st["state"].get(i, st["state"].get(str(i)))
+        if s is None:
+            continue
+        m[n].copy_(s["exp_avg"].reshape(m[n].shape))
+        v[n].copy_(s["exp_avg_sq"].reshape(v[n].shape))
+        head.step = int(float(s["step"]))
+
+
+def gather_metric_rows(rows: torch.Tensor, n_total: int, rank: int, world: int) -> torch.Tensor:
+    """Rank r holds the rows of images r, r + world, ...: -> the [n_total, 9] table in image order on every rank."""
+    if world == 1:
+        return rows
+    per = -(-n_total // world)
+    pad = torch.full((per, rows.shape[1]), float("nan"), dtype=rows.dtype, device=rows.device)
+    pad[:rows.shape[0]] = rows
+    parts = [torch.empty_like(pad) for _ in range(world)]
+    torch.distributed.all_gather(parts, pad)
+    return torch.stack([parts[i % world][i // world] for i in range(n_total)])
+
+
+def evaluate_depth(head, backbone, ds, cfg, rank, world, device) -> np.ndarray:
+    """The per-image metric table [n, 9] (float64) of the validation split."""
+    crop = DP.EIGEN_CROP if cfg["data"]["val"].get("eigen_crop", True) else None
+    mine = list(range(rank, len(ds), world))
+    table = torch.zeros(max(len(mine), 1), len(DP.METRICS), dtype=torch.float64, device=device)
+    for j, i in enumerate(mine):
+        img, depth = DD.load_pair(ds, i)
+        x = torch.from_numpy(DD.test_sample(img)).to(device)
+        gt = torch.from_numpy(np.ascontiguousarray(depth)).to(device)
+        head.evaluate_image(x, gt, table[j], backbone, crop=crop)
+    return gather_metric_rows(table[:len(mine)], len(ds), rank, world).cpu().numpy()
+
+
+def main_depth(args) -> dict:
+    opts = (args.cfg_options or []) + (args.options or [])
+    cfg = build_depth_config(args.config, opts, args.data_root)
+    work_dir = args.work_dir or cfg.get("work_dir") or os.path.join(
+        "work_dirs", os.path.splitext(os.path.basename(args.config))[0])
+    world = int(os.environ.get("WORLD_SIZE", 1)) if args.launcher == "pytorch" else 1
+    rank = int(os.environ.get("RANK", 0)) if world > 1 else 0
+    local = int(os.environ.get("LOCAL_RANK", args.local_rank)) if world > 1 else 0
+    device = torch.device("cuda", local)
+    torch.cuda.set_device(device)
+    if world > 1:
+        from . import dist as _dist
+        _dist.init(device, world)
+    os.makedirs(work_dir, exist_ok=True)
+    log_path = os.path.join(work_dir, time.strftime("%Y%m%d_%H%M%S") + ".log")
+
+    def log(msg):
+        if rank == 0:
+            print(msg, flush=True)
+            with open(log_path, "a") as f:
+                f.write(msg + "\n")
+
+    seed = args.seed if args.seed is not None else 0
+    if args.diff_seed:
+        seed += rank
+    random.seed(seed)
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    log(f"Config:\n{json.dumps(cfg, indent=1, default=str)}\nArguments: {json.dumps(vars(args))}\nseed {seed}, world {world}")
+
+    data = cfg["data"]
+    tr, va = data["train"], data["val"]
+    train_ds = DD.NYUDataset(tr["data_root"], tr["split"], tr.get("depth_scale", 1000))
+    val_ds = DD.NYUDataset(va["data_root"], va["split"], va.get("depth_scale", 1000))
+    backbone, C = build_backbone(args, device)
+    backbone.return_cls = True
+    hc = cfg["model"]["decode_head"]
+    head = DP.DepthHeadEngine(C, device, n_bins=hc.get("n_bins", 256), min_depth=hc.get("min_depth", 1e-3),
+                              max_depth=hc.get("max_depth", 10), upsample=hc.get("upsample", 4), seed=seed)
+
+    start, best = 0, None
+    resume = args.resume_from
+    if resume is None and args.auto_resume and os.path.exists(os.path.join(work_dir, "latest.pth")):
+        resume = os.path.join(work_dir, "latest.pth")
+    if resume:
+        ck = torch.load(resume, map_location="cpu", weights_only=False)
+        head.load_state_dict(ck["state_dict"])
+        load_depth_optimizer_state(head, ck["optimizer"])
+        start = int(ck["meta"]["iter"])
+        best = ck["meta"].get("best")
+        log(f"resumed from {resume} at iter {start}")
+
+    opt, lrc = cfg["optimizer"], cfg["lr_config"]
+    T = int(cfg["runner"]["max_iters"])
+    spg = int(data["samples_per_gpu"])
+    ckc, evc = cfg["checkpoint_config"], cfg["evaluation"]
+    ck_int, ev_int, keep = int(ckc["interval"]), int(evc["interval"]), int(ckc.get("max_keep_ckpts", -1))
+    log_int = int(cfg.get("log_config", {}).get("interval", 50))
+    clip = (cfg.get("optimizer_config") or {}).get("grad_clip")
+    onecycle = cfg.get("momentum_config") is not None
+    betas = tuple(opt.get("betas", (0.9, 0.999)))
+    key, rule = evc.get("save_best", "abs_rel"), evc.get("rule") or ("greater" if evc.get("save_best") in ("a1", "a2", "a3") else "less")
+    feeder = DD.DepthTrainFeeder(train_ds, spg, cfg["crop_size"], seed, rank, world, start, T, device,
+                                 workers=min(16, max(1, int(data.get("workers_per_gpu", 2)) * 2)))
+    results_path = os.path.join(work_dir, "eval_results.json")
+    results = json.load(open(results_path)) if (resume and os.path.exists(results_path)) else []
+    results = [r for r in results if r["iter"] <= start]
+    lr, beta1, skipped = 0.0, betas[0], 0
+    t0 = time.perf_counter()
+
+    def save(name, n):
+        path = os.path.join(work_dir, name)
+        torch.save({"meta": {"iter": n, "epoch": 0, "seed": seed, "time": time.asctime(), "best": best,
+                             "config": json.dumps(cfg, default=str)},
+                    "state_dict": head.state_dict(), "optimizer": depth_optimizer_state(head, opt, lr, beta1)}, path)
+        return path
+
+    try:
+        for it in range(start, T):
+            lr = DP.cosine_lr(it, opt["lr"], T, lrc.get("min_lr_ratio", 0.0), lrc.get("warmup_iters", 0) if lrc.get("warmup") else 0,
+                              lrc.get("warmup_ratio", 0.1))
+            beta1 = DP.onecycle_beta1(it, T) if onecycle else betas[0]
+            img, gt, _, valid = feeder.next()
+            n = it + 1
+            if world == 1 and not valid:
+                # the reference's loss is NaN here and poisons the head: the step is skipped, the parameters stay as they are
+                skipped += 1
+                log(f"Iter [{n}/{T}]\tskipped: no valid ground-truth pixel in the batch ({skipped} so far)")
+                out = None
+            else:
+                feats, cls = backbone(img)
+                out = head.train_step(feats, cls, gt, it)
+                if world > 1:  # a rank without a valid pixel joins with zero gradients; the loss statistics stay per rank
+                    torch.distributed.all_reduce(head.grads)
+                    head.grads.mul_(1.0 / world)
+                if clip:
+                    head.clip_grad_norm(float(clip["max_norm"]))
+                head.adamw_step(lr, opt.get("weight_decay", 0.01), (beta1, betas[1]))
+            if out is not None and (n % log_int == 0 or n == T):
+                ld, lg = out.tolist()
+                log(f"Iter [{n}/{T}]\tlr: {lr:.3e}, momentum: {beta1:.4f}, decode.loss_depth: {ld:.4f}, decode.loss_grad: {lg:.4f}, "
+                    f"loss: {ld + lg:.4f}, time: {(time.perf_counter() - t0) / max(1, n - start):.3f}")
+            if (n % ck_int == 0 or n == T) and rank == 0:
+                path = save(f"iter_{n}.pth", n)
+                shutil.copyfile(path, os.path.join(work_dir, "latest.pth"))
+                if keep > 0:
+                    old = sorted((int(f[5:-4]) for f in os.listdir(work_dir) if f.startswith("iter_") and f.endswith(".pth")))
+                    for m_ in old[:-keep]:
+                        os.remove(os.path.join(work_dir, f"iter_{m_}.pth"))
+            if not args.no_validate and (n % ev_int == 0 or n == T):
+                table = evaluate_depth(head, backbone, val_ds, cfg, rank, world, device)
+                met = DP.summarize(table)
+                log("Summary:\n" + " | ".join(f"{k} {v:.4f}" for k, v in met.items()))
+                results.append({"iter": n, **met})
+                if rank == 0:
+                    with open(results_path, "w") as f:
+                        json.dump(results, f, indent=1)
+                    v = met.get(key) if key else None
+                    if v is not None and not np.isnan(v) and (best is None or (v < best["value"] if rule == "less" else v > best["value"])):
+                        if best is not None and os.path.exists(os.path.join(work_dir, best["file"])):
+                            os.remove(os.path.join(work_dir, best["file"]))
+                        best = {"value": v, "iter": n, "file": f"best_{key}_iter_{n}.pth"}
+                        save(best["file"], n)
+    finally:
+        feeder.close()
+    return {"work_dir": work_dir, "results": results, "skipped": skipped}
 
 
 if __name__ == "__main__":

@@ -281,8 +281,12 @@ class ViTBackbone:
     out_indices [8, 9, 10, 11] is the last block).  One HipViT per padded input size, a few kept."""
     CACHE = 4
 
-    def __init__(self, state_dict: dict, patch: int, device, dtype: str = "bfloat16", denoiser=None):
+    def __init__(self, state_dict: dict, patch: int, device, dtype: str = "bfloat16", denoiser=None,
+                 return_cls: bool = False):
+        """return_cls: the call returns (features, cls [B, C]): the final-normed cls token of the ViT beside the features (the
+        depth probe's input; with a denoiser the features are the denoiser's and the cls token stays the ViT's own)."""
         self.sd, self.patch, self.device, self.dtype, self.denoiser = state_dict, patch, torch.device(device), dtype, denoiser
+        self.return_cls = return_cls
         self._engines = {}
 
     def _engine(self, hp: int, wp: int):
@@ -296,12 +300,15 @@ class ViTBackbone:
             self._engines[key] = HipViT(self.sd, self.patch, self.patch, (hp, wp), self.device, dtype=self.dtype)
         return self._engines[key]
 
-    def __call__(self, img: torch.Tensor) -> torch.Tensor:
+    def __call__(self, img: torch.Tensor):
         _, _, H, W = img.shape
         (t, b), (l, r) = center_pad(H, self.patch), center_pad(W, self.patch)
         x = torch.nn.functional.pad(img, (l, r, t, b)).contiguous()
+        cls = None
         with torch.no_grad():
-            f = self._engine(H + t + b, W + l + r).forward_features(x.float())
+            f = self._engine(H + t + b, W + l + r).forward_features(x.float(), return_cls=self.return_cls)
+            if self.return_cls:
+                f, cls = f
             if self.denoiser is not None:
                 f = self.denoiser(f.contiguous())
-        return f.contiguous()
+        return (f.contiguous(), cls) if self.return_cls else f.contiguous()

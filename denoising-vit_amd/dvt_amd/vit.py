@@ -66,6 +66,9 @@ _lib.register_signatures({
     "dvt_vit_gemm_qkv_x3": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dvt_vit_forward_f32x3": (_I, [C.POINTER(VitConfig), C.POINTER(VitWeights), _P, _P, _I, _I, _P, _P]),
     "dvt_vit_gemm_qkv": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, C.c_float, _P]),
+    "dvt_vit_forward_cls": (_I, [C.POINTER(VitConfig), C.POINTER(VitWeights), _P, _P, _P, _I, _I, _P, _P]),
+    "dvt_vit_forward_f32_cls": (_I, [C.POINTER(VitConfig), C.POINTER(VitWeights), _P, _P, _P, _I, _I, _P, _P]),
+    "dvt_vit_forward_f32x3_cls": (_I, [C.POINTER(VitConfig), C.POINTER(VitWeights), _P, _P, _P, _I, _I, _P, _P]),
     "dvt_vit_ln_cast_stats": (_I, [_P, _P, _P, _I, _I, C.c_float, _P]),
     "dvt_vit_gemm_residual_stats": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_float, _P]),
 })
@@ -349,9 +352,11 @@ class HipViT:
         return self._ws
 
     def forward_features(self, img: torch.Tensor, n_blocks: int | None = None,
-                         out: torch.Tensor | None = None, max_batch: int = 128) -> torch.Tensor:
+                         out: torch.Tensor | None = None, max_batch: int = 128, return_cls: bool = False):
         """img [B,3,H,W] fp32 (normalised) -> [B, grid_h, grid_w, dim] fp32 (NHWC), the final-norm'ed
-        patch tokens after `n_blocks` blocks.  `out` may be a slice of the feature store."""
+        patch tokens after `n_blocks` blocks.  `out` may be a slice of the feature store.
+        return_cls: -> (patch tokens, cls [B, dim] fp32), the final-norm'ed cls token of the same forward (the cls row
+        alone for the register models); the patch tokens are the same bits either way."""
         _lib.require_cuda(img)
         cfg = self.cfg
         if img.dtype != torch.float32 or tuple(img.shape[1:]) != (3, cfg.img_h, cfg.img_w):
@@ -368,12 +373,20 @@ class HipViT:
         ws = self._workspace(max(plan))
         L = _lib.lib()
         fwd = L.dvt_vit_forward_f32x3 if self.x3 else L.dvt_vit_forward_f32 if self.dtype == "float32" else L.dvt_vit_forward
+        if return_cls:
+            fwd_cls = (L.dvt_vit_forward_f32x3_cls if self.x3 else L.dvt_vit_forward_f32_cls if self.dtype == "float32"
+                       else L.dvt_vit_forward_cls)
+            cls = torch.empty((B, cfg.dim), device=self.device, dtype=torch.float32)
         b0 = 0
         for nb in plan:
-            _lib.check(fwd(C.byref(cfg), C.byref(self.weights), img[b0:].data_ptr(), out[b0:].data_ptr(), nb,
-                           n_blocks, ws.data_ptr(), _lib.stream()), "dvt_vit_forward")
+            if return_cls:
+                _lib.check(fwd_cls(C.byref(cfg), C.byref(self.weights), img[b0:].data_ptr(), out[b0:].data_ptr(),
+                                   cls[b0:].data_ptr(), nb, n_blocks, ws.data_ptr(), _lib.stream()), "dvt_vit_forward_cls")
+            else:
+                _lib.check(fwd(C.byref(cfg), C.byref(self.weights), img[b0:].data_ptr(), out[b0:].data_ptr(), nb,
+                               n_blocks, ws.data_ptr(), _lib.stream()), "dvt_vit_forward")
             b0 += nb
-        return out
+        return (out, cls) if return_cls else out
 
     def _memory_cap(self, max_batch: int) -> int:
         """`max_batch` bounded by what the device can hold NOW (the fp32 extractor's launches grew from 32 to 160

@@ -206,6 +206,16 @@ int dvt_vit_attention_log2q(const void* qk, const void* vt, void* out, int batch
 int dvt_vit_is_lab_build(void);
 int dvt_vit_debug_buffer(void* dev_u32);
 
+/* The three forwards with one more output: cls [batch, dim] fp32 = the final-LayerNorm'ed cls token of every image (for the
+ * register models the cls row alone), taken from the same residual stream as the patch tokens; `feat` gets the bits the plain
+ * entry point writes. */
+int dvt_vit_forward_cls(const DvtVitConfig* h_cfg, const DvtVitWeights* h_w, const float* img, float* feat, float* cls,
+                        int batch, int n_blocks, void* workspace, void* stream);
+int dvt_vit_forward_f32_cls(const DvtVitConfig* h_cfg, const DvtVitWeights* h_w, const float* img, float* feat, float* cls,
+                            int batch, int n_blocks, void* workspace, void* stream);
+int dvt_vit_forward_f32x3_cls(const DvtVitConfig* h_cfg, const DvtVitWeights* h_w, const float* img, float* feat, float* cls,
+                              int batch, int n_blocks, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
