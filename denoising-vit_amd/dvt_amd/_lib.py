@@ -29,6 +29,7 @@ HIP_SOURCES = [
     "dvt_stage3.hip",
     "dvt_seg.hip",
     "dvt_depth.hip",
+    "dvt_vis.hip",
     "dvt_prof.hip",
     "dvt_views.hip",
 ]

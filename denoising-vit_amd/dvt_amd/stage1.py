@@ -98,6 +98,12 @@ def get_args(argv=None):
                         "(dvt_fit_run_batched), further groups run on side streams; 1..16.  0 (default) = auto: 4 (round 6: +0.9 .. "
                         "1.8 % images/s at 1000 iterations; 0.58 instead of 0.46 images/s at 20000) -- each image in flight "
                         "holds its views + feature store (5.7 GB at ViT-B/14, 769 views); 1 = the reference's one fit at a time")
+    p.add_argument("--save_vis", action="store_true",
+                   help="write the reference's tiled picture (input crop; PCA / cluster / norm / similarity of the raw and of "
+                        "the denoised features; G; |h|; G + h) of --num_vis_samples random views plus the original image to "
+                        "<output_dir>/visualization/ for every --vis_freq-th image.  Off by default (the reference always "
+                        "draws it): the features written do not depend on it, the time per image does")
+    p.add_argument("--vis_font", type=str, default=None, help="TrueType / OpenType file for the tile's labels")
     args = p.parse_args(argv)
     if isinstance(args.input_size, int):
         args.input_size = (args.input_size, args.input_size)
@@ -229,6 +235,7 @@ class Stage1:
         self.timings = []
         self._idx_spare = []  # index streams drawn ahead for the next fit (numpy stream order kept)
         self._idx_queue = None  # look-ahead queue while `run` is active
+        self.vis_hook = None  # --save_vis: called as vis_hook(slot, engine) on the fit stream once a group is fitted
 
     def vit_launch_views(self, n_views: int) -> list:
         """Views of each extractor launch for an image of `n_views` views (what `extract` will do; reported by bench.py)."""
@@ -452,6 +459,9 @@ class Stage1:
                     for slot, den in zip(group, dens):
                         slot.raw_host.copy_(slot.features[-1], non_blocking=True)
                         slot.den_host.copy_(den, non_blocking=True)
+                    if self.vis_hook is not None:  # before the engines move on to the next group
+                        for slot, eng in zip(group, self.engines):
+                            self.vis_hook(slot, eng)
                     group[-1].fitted.record(self.s_fit)
                 fitted.put(group)
         except BaseException:
@@ -493,6 +503,53 @@ class Stage1:
         return raw_h, den_h
 
 
+VIS_SEED_OFFSET = 7919  # the tiles' views and k-means starts: RandomState(seed + VIS_SEED_OFFSET + image index)
+
+
+def _make_vis_hook(args, st, norm, device, first_index: int, vis_idx: dict, vis_out: dict):
+    """--save_vis (main_img_denoising.py:101-117): for every vis_freq-th image, the fitted modules are exported from the
+    image's engine, `forward(return_visualization=True)` runs on num_vis_samples random views plus the original image, and
+    the tile is composed on the fit stream; the uint8 picture goes to pinned memory and the retiring thread writes it.
+    The view indices come from a generator of their own, not from the global numpy stream of the fit's index draws."""
+    from .models import NeuralFeatureField, SingleImageDenoiser
+    from .utils import visualization as VZ
+    from .vis import VisEngine
+    # Built HERE, on the calling thread before the pipeline's threads start: the modules' constructors draw from torch's
+    # global CPU generator, whose state is put back afterwards (nothing else can draw from it meanwhile).
+    s = st.engines[0].s
+    with torch.random.fork_rng(devices=[]):
+        den = SingleImageDenoiser(s.noise_map_height, s.noise_map_width, s.feat_dim,
+                                  enable_residual_predictor=s.enable_residual_predictor).to(device)
+        field = NeuralFeatureField(s.feat_dim, s.base_resolution, s.max_resolution, s.n_levels, s.n_features_per_level,
+                                   s.log2_hashmap_size).to(device)
+    if s.enable_residual_predictor:
+        den.start_residual_predictor()
+    state = {"den": den, "field": field,
+             "eng": VisEngine(device, max_rows=s.noise_map_height * s.noise_map_width, max_channels=s.feat_dim, max_clusters=5)}
+    mean = torch.as_tensor(norm.mean, dtype=torch.float32, device=device).view(1, 3, 1, 1)
+    std = torch.as_tensor(norm.std, dtype=torch.float32, device=device).view(1, 3, 1, 1)
+
+    def denormalizer(img):
+        return img * std + mean
+
+    def hook(slot, engine):
+        filename = slot.tag[0]
+        idx = vis_idx.get(filename)
+        if idx is None or (first_index + idx) % max(1, args.vis_freq) != 0:
+            return
+        engine.export_modules(state["den"], state["field"])
+        seed = args.seed + VIS_SEED_OFFSET + first_index + idx
+        views = state["eng"].upload(VZ.view_indices(args.num_views, args.num_vis_samples, seed), torch.int64)  # pinned, non-blocking
+        tile, _, _ = VZ.compose_offline_tile(state["den"], state["field"], slot.features[views], slot.coords[views],
+                                             slot.views[views], device, denormalizer, getattr(args, "vis_font", None), seed,
+                                             state["eng"])
+        host = torch.empty(tile.shape, dtype=torch.uint8, pin_memory=True)
+        host.copy_(tile, non_blocking=True)
+        vis_out[filename] = host
+
+    return hook
+
+
 def main(args, rank: int = 0, world: int = 1, stage_factory=None, device=None):
     """The sweep of one rank.  `stage_factory(args, device)` builds the per-GPU engine (default:
     `Stage1`); tests inject a host-only stand-in to drive this function under gloo."""
@@ -523,6 +580,11 @@ def main(args, rank: int = 0, world: int = 1, stage_factory=None, device=None):
     # consumed by different host threads.
     view_rng = np.random.RandomState(args.seed + 1000003 * (rank + 1))
 
+    save_vis = bool(getattr(args, "save_vis", False))
+    vis_idx, vis_out = {}, {}  # --save_vis: image index by file name; finished tiles (pinned) by file name
+    if save_vis:
+        st.vis_hook = _make_vis_hook(args, st, norm, device, lo, vis_idx, vis_out)
+
     def jobs():
         for idx, filename in enumerate(names):
             filename = filename.strip().split(" ")[0]
@@ -533,6 +595,8 @@ def main(args, rank: int = 0, world: int = 1, stage_factory=None, device=None):
                     print(f"Skipping {filename}")
                     continue
                 paths = misc.output_paths(args.save_root, args.model, args.data_root, filename)
+            if save_vis:
+                vis_idx[filename] = idx
 
             def set_views(slot, filename=filename, idx=idx):
                 if args.synthetic:
@@ -554,6 +618,10 @@ def main(args, rank: int = 0, world: int = 1, stage_factory=None, device=None):
         if paths is not None:
             misc.atomic_save_npy(paths[0], raw_h.copy())  # [H, W, C]
             misc.atomic_save_npy(paths[1], den_h.copy())  # [1, H, W, C]
+        tile = vis_out.pop(filename, None) if save_vis else None
+        if tile is not None:  # main_img_denoising.py:114-117
+            from .utils import visualization as VZ
+            VZ.save_image(os.path.join(args.output_dir, "visualization", os.path.basename(filename)), tile.numpy())
         el = time.time() - start
         print(f"[rank {rank}] {filename}: done at {el:.2f}s")
         with open(os.path.join(args.output_dir, f"timings_rank{rank}.jsonl"), "a") as f:
