@@ -7,6 +7,7 @@ from . import s3  # noqa: F401  (stage-3 entry points)
 from . import seg  # noqa: F401  (segmentation-evaluation entry points)
 from . import depth  # noqa: F401  (depth-evaluation entry points)
 from . import vis  # noqa: F401  (visualisation entry points)
+from . import video  # noqa: F401  (video-demo entry points)
 from .fit import FitEngine, FitSettings  # noqa: F401
 from . import models  # noqa: F401
 

@@ -30,6 +30,7 @@ HIP_SOURCES = [
     "dvt_seg.hip",
     "dvt_depth.hip",
     "dvt_vis.hip",
+    "dvt_video.hip",
     "dvt_prof.hip",
     "dvt_views.hip",
 ]
