@@ -71,7 +71,10 @@ constexpr int STAGE_BYTES = (GBM + GBN) * GBK * 2;  // 32 KB
 // EPI_GELU_X3 / EPI_QKV_X3 (same mode): the outputs leave as (hi, lo) bf16 splits of the fp32 values -- GELU(h) as the
 // next GEMM's [hi | hi | lo] row (`out`, row stride 3 N), q | k as two [M, 2 dim] arrays (`out`, `out_lo`) and V^T as two
 // [batch, heads, 64, s_pad] arrays (`vt`, `vt_lo`): what the split kernels + the qkv prep kernels would write.
-enum { EPI_BIAS = 0, EPI_QKV = 1, EPI_GELU = 2, EPI_RESID = 3, EPI_EMBED = 4, EPI_F32 = 5, EPI_GELU_X3 = 6, EPI_QKV_X3 = 7 };
+// EPI_SWIGLU (ViT-g/14): W's rows arrive PACKED (dvt_vit_swiglu_pack_index) -- of a wave's 64 accumulator columns the first 32
+// are gates, the last 32 the values of the same 32 hidden units -- and `out` is the half-width [M, N / 2] silu(gate) * value.
+enum { EPI_BIAS = 0, EPI_QKV = 1, EPI_GELU = 2, EPI_RESID = 3, EPI_EMBED = 4, EPI_F32 = 5, EPI_GELU_X3 = 6, EPI_QKV_X3 = 7,
+       EPI_SWIGLU = 8 };
 #define IS_QKV(E) ((E) == EPI_QKV || (E) == EPI_QKV_X3)
 #define IS_GELU(E) ((E) == EPI_GELU || (E) == EPI_GELU_X3)
 #define IS_X3(E) ((E) == EPI_GELU_X3 || (E) == EPI_QKV_X3)
@@ -81,7 +84,7 @@ struct GemmBArgs {
   const bf16_t* W;
   int M, N, K;
   const float* bias;  // [N]
-  bf16_t* out;        // EPI_BIAS / EPI_GELU: [M, N]; EPI_QKV: qk [M, 2*dim]
+  bf16_t* out;        // EPI_BIAS / EPI_GELU: [M, N]; EPI_QKV: qk [M, 2*dim]; EPI_SWIGLU: [M, N / 2]
   bf16_t* vt;         // EPI_QKV: [batch, heads, 64, s_pad]
   bf16_t* out_lo;     // EPI_QKV_X3: the lo parts of q | k ...
   bf16_t* vt_lo;      // ... and of V^T
@@ -277,11 +280,46 @@ __device__ __forceinline__ void gelu_erf_pair(float& x0, float& x1) {
   x1 = r.y;
 }
 
+// silu(g) = g * sigmoid(g) = g / (1 + 2^(-g log2 e)), the exponential in the log2 domain as in the attention kernel (one
+// v_exp_f32).  The exponent is clamped at 126 so that 1 + 2^t stays finite: g = -100 gives -100 * 2^-126 (the true value,
+// -3.7e-42, is below every output format's resolution) instead of -100 / inf; g -> +large gives g / 1.  No inf, no NaN for
+// any finite g.  v_rcp_f32 is 1 ulp: far below the bf16 store.
+__device__ __forceinline__ float silu_log2(float g) {
+  const float e = __builtin_amdgcn_exp2f(fminf(g * -1.4426950408889634f, 126.f));
+  return g * __builtin_amdgcn_rcpf(1.f + e);
+}
+
 // Fused epilogues.  acc[i][j][r] = C[m0 + wm*64 + i*16 + 4*(lane>>4) + r][n0 + wn*64 + j*16 + (lane&15)]
 template <int EPI>
 __device__ __forceinline__ void gemm_epilogue(const GemmBArgs& p, f32x4 (&acc)[4][4], int m0, int n0,
                                               int wm, int wn, int lane) {
   const int g = lane >> 4, lc = lane & 15;
+  if constexpr (EPI == EPI_SWIGLU) {
+    // packed columns: acc[i][j] (j = 0, 1) are the gates of hidden units hb + j * 16 + lc, acc[i][j + 2] their values
+    const int ldo = p.N >> 1, hb = (n0 + wn * 64) >> 1;
+    const bool odd = lane & 1;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int n = n0 + wn * 64 + j * 16 + lc, h = hb + j * 16 + lc;
+      const float bg = p.bias != nullptr ? p.bias[n] : 0.f, bv = p.bias != nullptr ? p.bias[n + 32] : 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int mrow = m0 + wm * 64 + i * 16 + 4 * g;
+        float v[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = silu_log2(acc[i][j][r] + bg) * (acc[i][j + 2][r] + bv);
+#pragma unroll
+        for (int rp = 0; rp < 2; ++rp) {  // column pairs across lanes (l, l ^ 1), as the bf16 stores below
+          const float mine0 = v[rp], mine1 = v[rp + 2];
+          const float recv = __shfl_xor(odd ? mine0 : mine1, 1, 64);
+          const int r = odd ? rp + 2 : rp;
+          const uint32_t w = odd ? pack2(recv, mine1) : pack2(mine0, recv);
+          *reinterpret_cast<uint32_t*>(p.out + (size_t)(mrow + r) * ldo + (odd ? h - 1 : h)) = w;
+        }
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int n = n0 + wn * 64 + j * 16 + lc;
@@ -458,7 +496,7 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmBArgs& p, f32x4 (&ac
   constexpr int ROWS = NI * 16;
   const int g = lane >> 4, lc = lane & 15;
   // LayerNorm folded into this GEMM (see ln_fold): the accumulators are x . W'^T of the UN-normalised rows
-  const bool ln = (IS_QKV(EPI) || IS_GELU(EPI)) && p.ln_stats != nullptr;
+  const bool ln = (IS_QKV(EPI) || IS_GELU(EPI) || EPI == EPI_SWIGLU) && p.ln_stats != nullptr;
   float* blk = reinterpret_cast<float*>(blk0 != nullptr ? blk0 : smem + wave * EP_WAVE_BYTES);
   const int nb = n0 + wn * 64;
   if (IS_QKV(EPI) && n0 >= 2 * p.dim) {
@@ -539,7 +577,7 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmBArgs& p, f32x4 (&ac
   // waves of the CU cover that latency -- kept here because it is the natural place)
   const int c8_ln = (lane & 7) * 8;
   float4 cs0 = make_float4(0.f, 0.f, 0.f, 0.f), cs1 = cs0, bf0 = cs0, bf1 = cs0;
-  if (ln && EPI != EPI_RESID && EPI != EPI_EMBED && EPI != EPI_F32) {
+  if (ln && EPI != EPI_RESID && EPI != EPI_EMBED && EPI != EPI_F32 && EPI != EPI_SWIGLU) {
     cs0 = *reinterpret_cast<const float4*>(p.ln_cs + nb + c8_ln);
     cs1 = *reinterpret_cast<const float4*>(p.ln_cs + nb + c8_ln + 4);
     bf0 = *reinterpret_cast<const float4*>(p.bias + nb + c8_ln);
@@ -560,6 +598,53 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmBArgs& p, f32x4 (&ac
   // each wave only re-reads its own block: no workgroup barrier needed, only LDS completion
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   const int mb = m0 + wm * 64;
+  if constexpr (EPI == EPI_SWIGLU) {
+    // The block's columns are packed: [0, 32) gates, [32, 64) the values of the same 32 hidden units (nb / 2 ...).  A lane
+    // takes 8 units of one row -- 8 gates + 8 values out of LDS, 16 B of bf16 out; 4 lanes = the block's 64-B share of an
+    // output row (the wave next door, wn + 1, writes the other half of the 128-B line), 16 rows per pass.  The 16 lanes of a
+    // quarter wave read rows {0, 1, 8, 9} + 2 q of the pass: at the pitch of 68 floats rows two apart would share banks.
+    const int c8 = (lane & 3) * 8, ldo = p.N >> 1;
+    const int rsub = ((lane >> 2) & 1) + 8 * ((lane >> 3) & 1) + 2 * (lane >> 4);
+    alignas(16) float csg[8], csv[8], bfg[8], bfv[8];
+    if (ln) {
+#pragma unroll
+      for (int q = 0; q < 8; q += 4) {
+        *reinterpret_cast<float4*>(csg + q) = *reinterpret_cast<const float4*>(p.ln_cs + nb + c8 + q);
+        *reinterpret_cast<float4*>(csv + q) = *reinterpret_cast<const float4*>(p.ln_cs + nb + 32 + c8 + q);
+        *reinterpret_cast<float4*>(bfg + q) = *reinterpret_cast<const float4*>(p.bias + nb + c8 + q);
+        *reinterpret_cast<float4*>(bfv + q) = *reinterpret_cast<const float4*>(p.bias + nb + 32 + c8 + q);
+      }
+    }
+#pragma unroll 1
+    for (int it = 0; it < ROWS / 16; ++it) {
+      if (pf != nullptr && it == 1) pf_issue(*pf);
+      const int row = it * 16 + rsub;
+      alignas(16) float gt[8], vl[8];
+#pragma unroll
+      for (int q = 0; q < 8; q += 4) {
+        *reinterpret_cast<float4*>(gt + q) = *reinterpret_cast<const float4*>(blk + row * EP_LD + c8 + q);
+        *reinterpret_cast<float4*>(vl + q) = *reinterpret_cast<const float4*>(blk + row * EP_LD + 32 + c8 + q);
+      }
+      if (ln) {  // rstd * (acc - mean * cs) + b' on both halves
+        const float2 stv = *reinterpret_cast<const float2*>(blk + row * EP_LD + 64);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          gt[q] = fmaf(stv.y, gt[q] - stv.x * csg[q], bfg[q]);
+          vl[q] = fmaf(stv.y, vl[q] - stv.x * csv[q], bfv[q]);
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 8; ++q) gt[q] = silu_log2(gt[q]) * vl[q];
+      typedef unsigned u32x4s_t __attribute__((ext_vector_type(4)));
+      const u32x4s_t val = {pack2(gt[0], gt[1]), pack2(gt[2], gt[3]), pack2(gt[4], gt[5]), pack2(gt[6], gt[7])};
+      u32x4s_t* dst = reinterpret_cast<u32x4s_t*>(p.out + (size_t)(mb + row) * ldo + (nb >> 1) + c8);
+      if (p.nt_store)
+        __builtin_nontemporal_store(val, dst);
+      else
+        *dst = val;
+    }
+    return;
+  }
   if (EPI == EPI_RESID || EPI == EPI_EMBED || EPI == EPI_F32) {
     const int c4 = lc * 4;  // 16 lanes x float4 = one 64-float row; 4 rows per pass
     float4 gm = make_float4(1.f, 1.f, 1.f, 1.f);
@@ -704,16 +789,18 @@ __global__ __launch_bounds__(256) void ln_stats_finalize_kernel(const float2* __
 }
 
 // After the patch embedding (whose epilogue is not a residual epilogue): bf16(x) and exact two-pass (mu, rstd)
+// NV: float4 register slots per lane that hold the row (4: dim <= 1024, the S / B / L models; 6: dim <= 1536, ViT-g)
+template <int NV = 4>
 __global__ __launch_bounds__(256) void ln_cast_stats_kernel(const float* __restrict__ x, bf16_t* __restrict__ xb,
                                                             float2* __restrict__ stats, int rows, int dim, float eps) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows) return;
   const float4* xr = reinterpret_cast<const float4*>(x + (size_t)row * dim);
   const int nq = dim >> 2;
-  float4 v[4];
+  float4 v[NV];
   float sum = 0.f;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < NV; ++i) {
     const int q = lane + 64 * i;
     if (q < nq) {
       v[i] = xr[q];
@@ -727,7 +814,7 @@ __global__ __launch_bounds__(256) void ln_cast_stats_kernel(const float* __restr
   const float mean = wave_sum(sum) / (float)dim;
   float var = 0.f;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < NV; ++i) {
     const int q = lane + 64 * i;
     if (q < nq) {
       const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
@@ -736,6 +823,25 @@ __global__ __launch_bounds__(256) void ln_cast_stats_kernel(const float* __restr
   }
   const float rstd = rsqrtf(wave_sum(var) / (float)dim + eps);
   if (lane == 0) stats[row] = make_float2(mean, rstd);
+}
+
+// silu(gate) * value on a full-width bf16 row [gates | values] (dvt_vit_swiglu_act): 8 hidden units per thread
+__global__ __launch_bounds__(256) void swiglu_act_kernel(const uint4* __restrict__ h, uint4* __restrict__ hid, long long n8,
+                                                         int hq) {
+  for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < n8; q += (long long)gridDim.x * 256) {
+    const long long r = q / hq;
+    const int c = (int)(q - r * hq);
+    const uint4 gv = h[r * 2 * hq + c], vv = h[r * 2 * hq + hq + c];
+    const unsigned gw[4] = {gv.x, gv.y, gv.z, gv.w}, vw[4] = {vv.x, vv.y, vv.z, vv.w};
+    unsigned o[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float g0 = __uint_as_float(gw[i] << 16), g1 = __uint_as_float(gw[i] & 0xffff0000u);
+      const float v0 = __uint_as_float(vw[i] << 16), v1 = __uint_as_float(vw[i] & 0xffff0000u);
+      o[i] = pack2(silu_log2(g0) * v0, silu_log2(g1) * v1);
+    }
+    hid[q] = make_uint4(o[0], o[1], o[2], o[3]);
+  }
 }
 
 // sum over the 16 lanes of a DPP row (rotations inside the row: v_add_f32 with a row_ror modifier, no LDS traffic)
@@ -1366,7 +1472,8 @@ int launch_gemm(const GemmBArgs& a0, hipStream_t s) {
     a.tiles_full = nt / a.group * a.group;
     const dim3 grid8((a.M / 256) * nt);
     if (g_vit_stagger_pct > 0 && grid8.x > 512) {  // (a launch of fewer than two rounds has nothing to de-synchronise)
-      const double epi_us = EPI == EPI_RESID ? 20.0 : (IS_GELU(EPI) ? 10.5 : 5.6);
+      // (EPI_SWIGLU borrows the GELU epilogue's measured 10.5 us: its own has not been measured)
+      const double epi_us = EPI == EPI_RESID ? 20.0 : ((IS_GELU(EPI) || EPI == EPI_SWIGLU) ? 10.5 : 5.6);
       const double tile_us = 1.68 * (a.K / GBK) + epi_us;
       a.stagger_ticks = (int)(tile_us * 100.0 * g_vit_stagger_pct / 100.0);
     }
@@ -1537,7 +1644,8 @@ __global__ __launch_bounds__(256) void im2col_pairs_kernel(const float* __restri
 // ======================================================================================
 // LayerNorm: fp32 row -> bf16 row (or fp32 output for the final norm), one wave per row
 // ======================================================================================
-template <bool FINAL>
+// NV: float4 register slots per lane that hold the row (4: dim <= 1024; 6: dim <= 1536, ViT-g)
+template <bool FINAL, int NV = 4>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x,
                                                         const float* __restrict__ w,
                                                         const float* __restrict__ b,
@@ -1556,10 +1664,10 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   }
   const float4* xr = reinterpret_cast<const float4*>(x + in_row * dim);
   const int nq = dim >> 2;
-  float4 v[4];
+  float4 v[NV];
   float sum = 0.f;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < NV; ++i) {
     const int q = lane + 64 * i;
     if (q < nq) {
       v[i] = xr[q];
@@ -1569,7 +1677,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   const float mean = wave_sum(sum) / (float)dim;
   float var = 0.f;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < NV; ++i) {
     const int q = lane + 64 * i;
     if (q < nq) {
       const float a = v[i].x - mean, bq = v[i].y - mean, cq = v[i].z - mean, d = v[i].w - mean;
@@ -1578,7 +1686,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   }
   const float rstd = rsqrtf(wave_sum(var) / (float)dim + eps);
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < NV; ++i) {
     const int q = lane + 64 * i;
     if (q < nq) {
       const float4 ww = reinterpret_cast<const float4*>(w)[q];
@@ -2414,7 +2522,7 @@ int64_t vit_carve(const DvtVitConfig* c, int batch, char* base, VitWork* w) {
   // (the phantom rows store no V^T (GemmBArgs::vt_rows): `batch` images are what is written and read; the spare image keeps
   // the layout of the workspace as it was)
   t.vt = (bf16_t*)take(((int64_t)batch + 1) * c->s_pad * c->dim * 2);
-  t.hid = (bf16_t*)take(T * c->mlp_dim * 2);
+  t.hid = (bf16_t*)take(T * c->mlp_dim * 2);  // (SwiGLU: the half-width silu(gate) * value is all the fc1 GEMM writes)
   t.col = (bf16_t*)take(T * c->k_patch * 2);
   t.xb = (bf16_t*)take(T * c->dim * 2);
   t.st_part = (float2*)take((int64_t)(c->dim / 64) * T * 8);
@@ -2423,9 +2531,21 @@ int64_t vit_carve(const DvtVitConfig* c, int batch, char* base, VitWork* w) {
   return o;
 }
 
+// the final LayerNorm (fp32 out, prefix / pad rows dropped): the 4-slot instantiation up to dim 1024, 6 slots above (ViT-g)
+void launch_final_norm(const float* x, const float* w, const float* b, float* y, int rows, int dim, float eps, int s_pad,
+                       int n_tokens, int n_prefix, hipStream_t s) {
+  if (dim <= 1024)
+    hipLaunchKernelGGL((layernorm_kernel<true, 4>), dim3(dvt_cdiv(rows, 4)), dim3(256), 0, s, x, w, b, (bf16_t*)nullptr, y, rows,
+                       dim, eps, s_pad, n_tokens, n_prefix);
+  else
+    hipLaunchKernelGGL((layernorm_kernel<true, 6>), dim3(dvt_cdiv(rows, 4)), dim3(256), 0, s, x, w, b, (bf16_t*)nullptr, y, rows,
+                       dim, eps, s_pad, n_tokens, n_prefix);
+}
+
 int check_vit_cfg(const DvtVitConfig* c) {
-  if (!c || c->dim <= 0 || c->dim % 128 || c->dim > 1024 || c->heads * 64 != c->dim) return DVT_E_BADARG;
-  if (c->depth < 1 || c->depth > DVT_VIT_MAX_DEPTH || c->mlp_dim % 128) return DVT_E_BADARG;
+  if (!c || c->dim <= 0 || c->dim % 128 || c->dim > 1536 || c->heads * 64 != c->dim) return DVT_E_BADARG;
+  if (c->depth < 1 || c->depth > DVT_VIT_MAX_DEPTH || c->mlp_dim <= 0 || c->mlp_dim % 128) return DVT_E_BADARG;
+  if (c->mlp_kind != DVT_VIT_MLP_GELU && c->mlp_kind != DVT_VIT_MLP_SWIGLU) return DVT_E_BADARG;
   // token rows per image: a multiple of 32 (bf16 path; dvt_vit_config writes the next multiple of 128, the fp32 paths' need)
   if (c->s_pad % 32 || c->s_pad < c->n_tokens || c->k_patch % 64) return DVT_E_BADARG;
   if (c->n_prefix < 1 || c->n_prefix > 9 || (c->pos_has_cls != 0 && c->pos_has_cls != 1)) return DVT_E_BADARG;
@@ -2561,12 +2681,20 @@ extern "C" int dvt_vit_config(int dim, int depth, int patch, int stride, int img
 
 extern "C" int dvt_vit_config_reg(int dim, int depth, int patch, int stride, int img_h, int img_w,
                                   int n_reg_tokens, DvtVitConfig* c) {
+  return dvt_vit_config_ex(dim, depth, patch, stride, img_h, img_w, n_reg_tokens, DVT_VIT_MLP_GELU, c);
+}
+
+extern "C" int dvt_vit_config_ex(int dim, int depth, int patch, int stride, int img_h, int img_w, int n_reg_tokens,
+                                 int mlp_kind, DvtVitConfig* c) {
+  if (mlp_kind != DVT_VIT_MLP_GELU && mlp_kind != DVT_VIT_MLP_SWIGLU) return DVT_E_BADARG;
   if (!c || n_reg_tokens < 0 || n_reg_tokens > 8 || dim <= 0 || dim % 64 || patch <= 0 || stride <= 0 || img_h < patch || img_w < patch)
     return DVT_E_BADARG;
   c->dim = dim;
   c->depth = depth;
   c->heads = dim / 64;
-  c->mlp_dim = 4 * dim;
+  // SwiGLU: the hidden width of timm's SwiGLUPacked / DINOv2's SwiGLUFFNFused at mlp_ratio 4, (int(4 dim * 2 / 3) + 7) / 8 * 8
+  c->mlp_dim = mlp_kind == DVT_VIT_MLP_SWIGLU ? (4 * dim * 2 / 3 + 7) / 8 * 8 : 4 * dim;
+  c->mlp_kind = mlp_kind;
   c->patch = patch;
   c->stride = stride;
   c->img_h = img_h;
@@ -2613,6 +2741,41 @@ extern "C" int dvt_vit_gemm_lnfold(const void* x, const void* w, const float* b,
   return launch_gemm<EPI_BIAS>(a, (hipStream_t)stream);
 }
 
+extern "C" int dvt_vit_swiglu_pack_index(int p, int n_hidden) {
+  if (n_hidden <= 0 || n_hidden % 32 || p < 0 || p >= 2 * n_hidden) return -1;
+  const int blk = p >> 6, q = p & 63;
+  return q < 32 ? 32 * blk + q : n_hidden + 32 * blk + (q - 32);
+}
+
+// The SwiGLU fc1 GEMM as dvt_vit_forward launches it for ViT-g (EPI_SWIGLU): y [m, n_hidden] = silu(gate) * value from the
+// PACKED [2 n_hidden, k] weights, optionally with the LayerNorm folded
+extern "C" int dvt_vit_gemm_swiglu(const void* x, const void* w, const float* b, void* y, int m, int n_hidden, int k,
+                                   const void* ln_stats, const float* ln_cs, void* stream) {
+  if (!x || !w || !y || (ln_stats == nullptr) != (ln_cs == nullptr) || n_hidden <= 0 || n_hidden % 64) return DVT_E_BADARG;
+  if (ln_stats != nullptr && b == nullptr) return DVT_E_BADARG;  // (the folded epilogue reads b' unconditionally)
+  GemmBArgs a{};
+  a.A = (const bf16_t*)x; a.W = (const bf16_t*)w; a.M = m; a.N = 2 * n_hidden; a.K = k;
+  a.bias = b; a.out = (bf16_t*)y;
+  a.lda = a.ldw = k;
+  a.ln_stats = (const float2*)ln_stats;
+  a.ln_cs = ln_cs;
+  return launch_gemm<EPI_SWIGLU>(a, (hipStream_t)stream);
+}
+
+// hid [m, n_hidden] (bf16) = silu(h[:, :n_hidden]) * h[:, n_hidden:] of a full-width h [m, 2 n_hidden] (bf16, the checkpoint's
+// column order): the UNFUSED form of the SwiGLU fc1 epilogue (dvt_vit_gemm_bias + this), kept for the A/B of
+// tools/bench_vitg.py; the extractor does not launch it
+extern "C" int dvt_vit_swiglu_act(const void* h, void* hid, long long m, int n_hidden, void* stream) {
+  if (!h || !hid || m < 0 || n_hidden <= 0 || n_hidden % 8) return DVT_E_BADARG;
+  if (m == 0) return 0;
+  const long long n8 = m * (n_hidden / 8);
+  const int blocks = (int)((n8 + 255) / 256 < 256 * 32 ? (n8 + 255) / 256 : 256 * 32);
+  hipLaunchKernelGGL(swiglu_act_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint4*)h, (uint4*)hid, n8,
+                     n_hidden / 8);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int dvt_vit_gemm_residual(const void* a_in, const void* w, const float* b, const float* gamma,
                                      float* x, int m, int n, int k, void* stream) {
   if (!a_in || !w || !gamma || !x) return DVT_E_BADARG;
@@ -2650,10 +2813,14 @@ extern "C" int dvt_vit_gemm_qkv(const void* x, const void* w, const float* b, vo
 
 // xb = bf16(x) and two-pass (mean, rstd) of every row: the kernel behind the patch embedding of the folded forward
 extern "C" int dvt_vit_ln_cast_stats(const float* x, void* xb, void* stats, int rows, int dim, float eps, void* stream) {
-  if (!x || !xb || !stats || rows < 0 || dim <= 0 || dim % 4 || dim > 1024) return DVT_E_BADARG;
+  if (!x || !xb || !stats || rows < 0 || dim <= 0 || dim % 4 || dim > 1536) return DVT_E_BADARG;
   if (rows == 0) return 0;
-  hipLaunchKernelGGL(ln_cast_stats_kernel, dim3(dvt_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, (bf16_t*)xb,
-                     (float2*)stats, rows, dim, eps);
+  if (dim <= 1024)
+    hipLaunchKernelGGL(ln_cast_stats_kernel<4>, dim3(dvt_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, (bf16_t*)xb,
+                       (float2*)stats, rows, dim, eps);
+  else
+    hipLaunchKernelGGL(ln_cast_stats_kernel<6>, dim3(dvt_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, (bf16_t*)xb,
+                       (float2*)stats, rows, dim, eps);
   DVT_CHECK_LAUNCH();
   return 0;
 }
@@ -2723,10 +2890,14 @@ extern "C" int dvt_vit_gemm_qkv_x3(const void* a_in, const void* w, const float*
 
 extern "C" int dvt_vit_layernorm(const float* x, const float* w, const float* b, void* y, int rows,
                                  int dim, float eps, void* stream) {
-  if (!x || !w || !b || !y || rows < 0 || dim <= 0 || dim % 4 || dim > 1024) return DVT_E_BADARG;
+  if (!x || !w || !b || !y || rows < 0 || dim <= 0 || dim % 4 || dim > 1536) return DVT_E_BADARG;
   if (rows == 0) return 0;
-  hipLaunchKernelGGL(layernorm_kernel<false>, dim3(dvt_cdiv(rows, 4)), dim3(256), 0,
-                     (hipStream_t)stream, x, w, b, (bf16_t*)y, (float*)nullptr, rows, dim, eps, 0, 0, 0);
+  if (dim <= 1024)
+    hipLaunchKernelGGL((layernorm_kernel<false, 4>), dim3(dvt_cdiv(rows, 4)), dim3(256), 0,
+                       (hipStream_t)stream, x, w, b, (bf16_t*)y, (float*)nullptr, rows, dim, eps, 0, 0, 0);
+  else
+    hipLaunchKernelGGL((layernorm_kernel<false, 6>), dim3(dvt_cdiv(rows, 4)), dim3(256), 0,
+                       (hipStream_t)stream, x, w, b, (bf16_t*)y, (float*)nullptr, rows, dim, eps, 0, 0, 0);
   DVT_CHECK_LAUNCH();
   return 0;
 }
@@ -2932,15 +3103,14 @@ extern "C" int dvt_vit_forward(const DvtVitConfig* c, const DvtVitWeights* w, co
     const DvtVitBlockWeights& bw = w->blocks[l];
     fuse_ln = fuse_ln && bw.qkv_wf && bw.qkv_cs && bw.qkv_bf && bw.fc1_wf && bw.fc1_cs && bw.fc1_bf;
   }
+  const bool swiglu = c->mlp_kind == DVT_VIT_MLP_SWIGLU;
   const int n_part = D / 64;
   auto finalize_stats = [&]() {
     hipLaunchKernelGGL(ln_stats_finalize_kernel, dim3(dvt_cdiv(T, 256)), dim3(256), 0, s, (const float2*)k.st_part,
                        n_part, T, 1.0f / (float)D, c->ln_eps, k.stats);
   };
   if (fuse_ln) {
-    hipLaunchKernelGGL(ln_cast_stats_kernel, dim3(dvt_cdiv(T, 4)), dim3(256), 0, s, (const float*)k.x, k.xb, k.stats, T, D,
-                       c->ln_eps);
-    DVT_CHECK_LAUNCH();
+    DVT_TRY(dvt_vit_ln_cast_stats(k.x, k.xb, k.stats, T, D, c->ln_eps, s));
   }
   bool log2q = g_vit_attn_log2q != 0;
 #ifdef DVT_LAB
@@ -2980,8 +3150,14 @@ extern "C" int dvt_vit_forward(const DvtVitConfig* c, const DvtVitWeights* w, co
       a.A = fuse_ln ? k.xb : k.xn; a.W = (const bf16_t*)(fuse_ln ? bw.fc1_wf : bw.fc1_w); a.M = T; a.N = c->mlp_dim; a.K = D;
       a.bias = fuse_ln ? bw.fc1_bf : bw.fc1_b; a.out = k.hid;
       if (fuse_ln) { a.ln_stats = k.stats; a.ln_cs = bw.fc1_cs; }
-      a.work = 2.0 * rows * (double)c->mlp_dim * D;
-      DVT_TRY(launch_gemm<EPI_GELU>(a, s));
+      if (swiglu) {  // packed [2 mlp_dim, dim] weights -> the half-width silu(gate) * value
+        a.N = 2 * c->mlp_dim;
+        a.work = 2.0 * rows * 2.0 * c->mlp_dim * D;
+        DVT_TRY(launch_gemm<EPI_SWIGLU>(a, s));
+      } else {
+        a.work = 2.0 * rows * (double)c->mlp_dim * D;
+        DVT_TRY(launch_gemm<EPI_GELU>(a, s));
+      }
     }
     {
       GemmBArgs a{};
@@ -2999,9 +3175,7 @@ extern "C" int dvt_vit_forward(const DvtVitConfig* c, const DvtVitWeights* w, co
 #undef DVT_TRY
   // final LayerNorm, drop cls/pad rows, NHWC fp32 straight into the feature store
   const int out_rows = batch * (c->n_tokens - c->n_prefix);
-  hipLaunchKernelGGL(layernorm_kernel<true>, dim3(dvt_cdiv(out_rows, 4)), dim3(256), 0, s, k.x,
-                     w->norm_w, w->norm_b, (bf16_t*)nullptr, feat, out_rows, D, c->ln_eps, c->s_pad,
-                     c->n_tokens, c->n_prefix);
+  launch_final_norm(k.x, w->norm_w, w->norm_b, feat, out_rows, D, c->ln_eps, c->s_pad, c->n_tokens, c->n_prefix, s);
   DVT_CHECK_LAUNCH();
   return 0;
 }
@@ -3015,8 +3189,7 @@ extern "C" int dvt_vit_forward_cls(const DvtVitConfig* c, const DvtVitWeights* w
   if (rc) return rc;
   VitWork k;
   vit_carve(c, batch, (char*)workspace, &k);
-  hipLaunchKernelGGL(layernorm_kernel<true>, dim3(dvt_cdiv(batch, 4)), dim3(256), 0, (hipStream_t)stream, k.x, w->norm_w,
-                     w->norm_b, (bf16_t*)nullptr, cls, batch, c->dim, c->ln_eps, c->s_pad, 1, 0);
+  launch_final_norm(k.x, w->norm_w, w->norm_b, cls, batch, c->dim, c->ln_eps, c->s_pad, 1, 0, (hipStream_t)stream);
   DVT_CHECK_LAUNCH();
   return 0;
 }

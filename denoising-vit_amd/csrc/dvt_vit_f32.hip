@@ -43,6 +43,7 @@ inline int64_t up256b(int64_t x) { return (x + 255) / 256 * 256; }
 
 struct VitWorkF {
   float *x, *xn, *qkv, *ao, *hid, *tmp, *col;
+  float* hid2;  // SwiGLU: the full-width fc1 product [T, 2 mlp_dim] (gates | values)
 };
 
 // rows of the linear layers' launches: batch * s_pad rounded up to whole 128-row tiles of the 128 x 128 x 32 GEMM (round 6: s_pad
@@ -66,6 +67,7 @@ int64_t carve_f32(const DvtVitConfig* c, int batch, char* base, VitWorkF* w) {
   t.hid = take(T * c->mlp_dim);
   t.tmp = take(T * c->dim);
   t.col = take(T * c->k_patch);
+  t.hid2 = c->mlp_kind == DVT_VIT_MLP_SWIGLU ? take(T * 2 * c->mlp_dim) : nullptr;
   if (w) *w = t;
   return o;
 }
@@ -165,7 +167,8 @@ __global__ __launch_bounds__(256) void split3_kernel(const float4* __restrict__ 
 }
 
 // SPLIT: y is a bf16 [rows, 3 * dim] row of split values instead of fp32 [rows, dim]
-template <bool FINAL, bool SPLIT = false>
+// NV: float4 register slots per lane that hold the row (4: dim <= 1024; 6: dim <= 1536, ViT-g)
+template <bool FINAL, bool SPLIT = false, int NV = 4>
 __global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                             const float* __restrict__ b, float* __restrict__ y,
                                                             int rows, int dim, float eps, int s_pad, int n_tokens,
@@ -181,10 +184,10 @@ __global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* __restr
   }
   const float4* xr = reinterpret_cast<const float4*>(x + in_row * dim);
   const int nq = dim >> 2;
-  float4 v[4];
+  float4 v[NV];
   float sum = 0.f;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < NV; ++i) {
     const int q = lane + 64 * i;
     if (q < nq) {
       v[i] = xr[q];
@@ -194,7 +197,7 @@ __global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* __restr
   const float mean = wave_sum(sum) / (float)dim;
   float var = 0.f;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < NV; ++i) {
     const int q = lane + 64 * i;
     if (q < nq) {
       const float a = v[i].x - mean, bq = v[i].y - mean, cq = v[i].z - mean, d = v[i].w - mean;
@@ -203,7 +206,7 @@ __global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* __restr
   }
   const float rstd = rsqrtf(wave_sum(var) / (float)dim + eps);
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < NV; ++i) {
     const int q = lane + 64 * i;
     if (q < nq) {
       const float4 ww = reinterpret_cast<const float4*>(w)[q], bb = reinterpret_cast<const float4*>(b)[q];
@@ -226,6 +229,38 @@ __global__ __launch_bounds__(256) void gelu_f32_kernel(float4* __restrict__ h, l
     v.w = 0.5f * v.w * (1.0f + erff(v.w * 0.70710678118654752f));
     h[q] = v;
   }
+}
+
+// hid[r, j] = silu(h[r, j]) * h[r, n_hidden + j] (timm SwiGLUPacked: gates first): the SwiGLU MLP of ViT-g between its fp32
+// GEMMs.  silu(g) = g / (1 + 2^(-g log2 e)), exponent clamped at 126 (finite for every finite g), IEEE division.
+__global__ __launch_bounds__(256) void swiglu_f32_kernel(const float4* __restrict__ h, float4* __restrict__ hid, long long nq,
+                                                         int hq) {
+  auto silu = [](float g) { return g / (1.0f + __builtin_amdgcn_exp2f(fminf(g * -1.4426950408889634f, 126.f))); };
+  for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long long)gridDim.x * 256) {
+    const long long r = q / hq;
+    const int c = (int)(q - r * hq);
+    const float4 g = h[r * 2 * hq + c], v = h[r * 2 * hq + hq + c];
+    hid[q] = make_float4(silu(g.x) * v.x, silu(g.y) * v.y, silu(g.z) * v.z, silu(g.w) * v.w);
+  }
+}
+
+// the fp32 LayerNorm launches: 4 register slots up to dim 1024, 6 above (ViT-g, dim 1536)
+void launch_ln_f32(const float* x, const float* w, const float* b, float* y, int rows, int dim, float eps, hipStream_t s) {
+  if (dim <= 1024)
+    hipLaunchKernelGGL((layernorm_f32_kernel<false, false, 4>), dim3(dvt_cdiv(rows, 4)), dim3(256), 0, s, x, w, b, y, rows, dim,
+                       eps, 0, 0, 0);
+  else
+    hipLaunchKernelGGL((layernorm_f32_kernel<false, false, 6>), dim3(dvt_cdiv(rows, 4)), dim3(256), 0, s, x, w, b, y, rows, dim,
+                       eps, 0, 0, 0);
+}
+void launch_final_ln_f32(const float* x, const float* w, const float* b, float* y, int rows, int dim, float eps, int s_pad,
+                         int n_tokens, int n_prefix, hipStream_t s) {
+  if (dim <= 1024)
+    hipLaunchKernelGGL((layernorm_f32_kernel<true, false, 4>), dim3(dvt_cdiv(rows, 4)), dim3(256), 0, s, x, w, b, y, rows, dim,
+                       eps, s_pad, n_tokens, n_prefix);
+  else
+    hipLaunchKernelGGL((layernorm_f32_kernel<true, false, 6>), dim3(dvt_cdiv(rows, 4)), dim3(256), 0, s, x, w, b, y, rows, dim,
+                       eps, s_pad, n_tokens, n_prefix);
 }
 
 // x += gamma * y  (timm Block: x = x + ls(f(norm(x))))
@@ -371,7 +406,8 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(const float* __restr
 }  // namespace
 
 extern "C" int64_t dvt_vit_workspace_bytes_f32(const DvtVitConfig* c, int batch) {
-  if (!c || batch <= 0 || c->s_pad % 32 || c->dim % 64 || c->heads * 64 != c->dim) return -1;
+  if (!c || batch <= 0 || c->s_pad % 32 || c->dim % 64 || c->dim > 1536 || c->heads * 64 != c->dim) return -1;
+  if (c->mlp_kind != DVT_VIT_MLP_GELU && c->mlp_kind != DVT_VIT_MLP_SWIGLU) return -1;
   return carve_f32(c, batch, nullptr, nullptr);
 }
 
@@ -409,6 +445,7 @@ int64_t carve_x3(const DvtVitConfig* c, int batch, char* base, VitWorkX3* w) {
 
 extern "C" int64_t dvt_vit_workspace_bytes_f32x3(const DvtVitConfig* c, int batch) {
   if (!c || batch <= 0 || c->s_pad % 128 || c->dim % 128 || c->heads * 64 != c->dim || c->k_patch % 64) return -1;
+  if (c->mlp_kind != DVT_VIT_MLP_GELU || c->dim > 1024) return -1;  // bf16x3: GELU MLPs, rows of at most 1024 (see the forward)
   return carve_x3(c, batch, nullptr, nullptr);
 }
 
@@ -445,6 +482,9 @@ extern "C" int dvt_vit_forward_f32x3(const DvtVitConfig* c, const DvtVitWeights*
   if (!c || !w || !img || !feat || !workspace || batch <= 0 || n_blocks < 0 || n_blocks > c->depth)
     return DVT_E_BADARG;
   if (c->s_pad % 128 || c->dim % 128 || c->heads * 64 != c->dim || c->k_patch % 64 || c->mlp_dim % 128) return DVT_E_BADARG;
+  // the split epilogues exist for the GELU MLP only, and the split LayerNorm holds a row in four register slots: the SwiGLU
+  // MLP (ViT-g) and rows wider than 1024 are refused, not approximated
+  if (c->mlp_kind != DVT_VIT_MLP_GELU || c->dim > 1024) return DVT_E_BADARG;
   hipStream_t s = (hipStream_t)stream;
   VitWorkX3 k;
   carve_x3(c, batch, (char*)workspace, &k);
@@ -521,7 +561,9 @@ extern "C" int dvt_vit_forward_f32(const DvtVitConfig* c, const DvtVitWeights* w
                                    int batch, int n_blocks, void* workspace, void* stream) {
   if (!c || !w || !img || !feat || !workspace || batch <= 0 || n_blocks < 0 || n_blocks > c->depth)
     return DVT_E_BADARG;
-  if (c->s_pad % 32 || c->dim % 64 || c->heads * 64 != c->dim || c->k_patch % 4) return DVT_E_BADARG;
+  if (c->s_pad % 32 || c->dim % 64 || c->dim > 1536 || c->heads * 64 != c->dim || c->k_patch % 4) return DVT_E_BADARG;
+  if (c->mlp_kind != DVT_VIT_MLP_GELU && c->mlp_kind != DVT_VIT_MLP_SWIGLU) return DVT_E_BADARG;
+  const bool swiglu = c->mlp_kind == DVT_VIT_MLP_SWIGLU;
   hipStream_t s = (hipStream_t)stream;
   VitWorkF k;
   carve_f32(c, batch, (char*)workspace, &k);
@@ -542,8 +584,7 @@ extern "C" int dvt_vit_forward_f32(const DvtVitConfig* c, const DvtVitWeights* w
   DVT_CHECK_LAUNCH();
   for (int l = 0; l < n_blocks; ++l) {
     const DvtVitBlockWeights& bw = w->blocks[l];
-    hipLaunchKernelGGL(layernorm_f32_kernel<false>, dim3(dvt_cdiv(T, 4)), dim3(256), 0, s, k.x, bw.norm1_w,
-                       bw.norm1_b, k.xn, T, D, c->ln_eps, 0, 0, 0);
+    launch_ln_f32(k.x, bw.norm1_w, bw.norm1_b, k.xn, T, D, c->ln_eps, s);
     DVT_CHECK_LAUNCH();
     DVT_TRY(dvt_linear_fwd_big(k.xn, (const float*)bw.qkv_w, bw.qkv_b, k.qkv, Tg, 3 * D, D, s));
     DVT_TRY(dvt_vit_attention_f32(k.qkv, k.ao, batch, c->heads, c->s_pad, c->n_tokens, s));
@@ -558,10 +599,24 @@ extern "C" int dvt_vit_forward_f32(const DvtVitConfig* c, const DvtVitWeights* w
                          (const float4*)bw.ls1, nqD, D / 4);
       DVT_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(layernorm_f32_kernel<false>, dim3(dvt_cdiv(T, 4)), dim3(256), 0, s, k.x, bw.norm2_w,
-                       bw.norm2_b, k.xn, T, D, c->ln_eps, 0, 0, 0);
+    launch_ln_f32(k.x, bw.norm2_w, bw.norm2_b, k.xn, T, D, c->ln_eps, s);
     DVT_CHECK_LAUNCH();
-    if (fuse) {
+    if (swiglu) {
+      // fc1 [Tg, 2 mlp_dim] (gates | values, the checkpoint's row order) -> silu(g) * v as a row-local kernel (this path is
+      // bound by the fp32 GEMMs) -> fc2 with K = mlp_dim
+      DVT_TRY(dvt_linear_fwd_big(k.xn, (const float*)bw.fc1_w, bw.fc1_b, k.hid2, Tg, 2 * c->mlp_dim, D, s));
+      hipLaunchKernelGGL(swiglu_f32_kernel, dim3(ew_blocks), dim3(256), 0, s, (const float4*)k.hid2, (float4*)k.hid,
+                         (long long)Tg * c->mlp_dim / 4, c->mlp_dim / 4);
+      DVT_CHECK_LAUNCH();
+      if (fuse) {
+        DVT_TRY(dvt_linear_fwd_big_epi(k.hid, (const float*)bw.fc2_w, bw.fc2_b, k.x, Tg, D, c->mlp_dim, 2, bw.ls2, s));
+      } else {
+        DVT_TRY(dvt_linear_fwd_big(k.hid, (const float*)bw.fc2_w, bw.fc2_b, k.tmp, Tg, D, c->mlp_dim, s));
+        hipLaunchKernelGGL(resid_f32_kernel, dim3(ew_blocks), dim3(256), 0, s, (float4*)k.x, (const float4*)k.tmp,
+                           (const float4*)bw.ls2, nqD, D / 4);
+        DVT_CHECK_LAUNCH();
+      }
+    } else if (fuse) {
       DVT_TRY(dvt_linear_fwd_big_epi(k.xn, (const float*)bw.fc1_w, bw.fc1_b, k.hid, Tg, c->mlp_dim, D, 1, nullptr, s));
       DVT_TRY(dvt_linear_fwd_big_epi(k.hid, (const float*)bw.fc2_w, bw.fc2_b, k.x, Tg, D, c->mlp_dim, 2, bw.ls2, s));
     } else {
@@ -577,8 +632,7 @@ extern "C" int dvt_vit_forward_f32(const DvtVitConfig* c, const DvtVitWeights* w
   }
 #undef DVT_TRY
   const int out_rows = batch * (c->n_tokens - c->n_prefix);
-  hipLaunchKernelGGL(layernorm_f32_kernel<true>, dim3(dvt_cdiv(out_rows, 4)), dim3(256), 0, s, k.x, w->norm_w,
-                     w->norm_b, feat, out_rows, D, c->ln_eps, c->s_pad, c->n_tokens, c->n_prefix);
+  launch_final_ln_f32(k.x, w->norm_w, w->norm_b, feat, out_rows, D, c->ln_eps, c->s_pad, c->n_tokens, c->n_prefix, s);
   DVT_CHECK_LAUNCH();
   return 0;
 }
@@ -591,8 +645,7 @@ extern "C" int dvt_vit_forward_f32_cls(const DvtVitConfig* c, const DvtVitWeight
   if (rc) return rc;
   VitWorkF k;
   carve_f32(c, batch, (char*)workspace, &k);
-  hipLaunchKernelGGL(layernorm_f32_kernel<true>, dim3(dvt_cdiv(batch, 4)), dim3(256), 0, (hipStream_t)stream, k.x, w->norm_w,
-                     w->norm_b, cls, batch, c->dim, c->ln_eps, c->s_pad, 1, 0);
+  launch_final_ln_f32(k.x, w->norm_w, w->norm_b, cls, batch, c->dim, c->ln_eps, c->s_pad, 1, 0, (hipStream_t)stream);
   DVT_CHECK_LAUNCH();
   return 0;
 }

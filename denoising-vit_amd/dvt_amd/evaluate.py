@@ -468,6 +468,9 @@ def metrics_table(met: dict, classes) -> str:
 # ================================================================================================ training
 def main(argv=None) -> dict:
     args = get_args(argv)
+    # the probe heads' kernels have only been built and measured for the S / B / L widths: a wider backbone stops here, by name
+    from .vit import require_consumer_width
+    require_consumer_width(args.backbone_type, "linear-probe evaluation")
     if args.task == "depth":
         return main_depth(args)
     opts = (args.cfg_options or []) + (args.options or [])

@@ -11,8 +11,9 @@ Differences forced by the environment (documented in DESIGN.md):
     does when the pretrained weights cannot be loaded -- features of a random ViT written to
     disk would be skipped forever by the existence-based resume.  Random init (seed 0) is
     available only on request (`allow_random_init=True`: synthetic benchmarks and tests).
-  * only the DINOv2 S/B/L backbones (with / without registers) are built; the other ids of
-    the reference's MODEL_LIST raise NotImplementedError (out of scope).
+  * only the DINOv2 S/B/L/g backbones (with / without registers) are built; the other ids of
+    the reference's MODEL_LIST raise NotImplementedError (out of scope).  ViT-g/14
+    (dim 1536, 40 blocks, SwiGLU MLP) runs in bfloat16 and exact float32; matmul="high" is refused.
   * the stride override (vit_wrapper.py:78-91) is honoured by the im2col kernel, but a
     grid other than the checkpoint's 37x37 is served by resampling pos_embed on the host (timm's
     resample_abs_pos_embed restated); the *_reg4_* models carry 4 register tokens (prefix tokens
@@ -156,7 +157,7 @@ class PretrainedViTWrapper(nn.Module):
             # O(1) LayerScale / biases / norm affines: with DINOv2's LayerScale init (1e-5) twelve
             # random blocks would be a numerical no-op and neither parity nor power draw would mean much
             sd = _vit.random_state_dict(self.spec.dim, self.spec.depth, self.spec.patch, n_tokens,
-                                        seed=0, well_conditioned=True, n_reg=self.spec.n_reg)
+                                        seed=0, well_conditioned=True, n_reg=self.spec.n_reg, mlp=self.spec.mlp)
         # timm data config of the DINOv2 models: ImageNet mean/std
         return sd, Compose([Normalize(IMAGENET_MEAN, IMAGENET_STD)])
 

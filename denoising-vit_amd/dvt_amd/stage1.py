@@ -553,6 +553,11 @@ def _make_vis_hook(args, st, norm, device, first_index: int, vis_idx: dict, vis_
 def main(args, rank: int = 0, world: int = 1, stage_factory=None, device=None):
     """The sweep of one rank.  `stage_factory(args, device)` builds the per-GPU engine (default:
     `Stage1`); tests inject a host-only stand-in to drive this function under gloo."""
+    # Before anything is written: the per-image fit, the loss rows and VisEngine hold a feature row in a fixed number of register
+    # slots.  A model wider than that stops HERE -- a feature file written before a later stop would be skipped forever by the
+    # existence-based resume.
+    from .vit import require_consumer_width
+    require_consumer_width(getattr(args, "model", None), "stage-1 fit")
     os.makedirs(args.output_dir, exist_ok=True)
     misc.fix_random_seeds(args.seed)
     if rank == 0:

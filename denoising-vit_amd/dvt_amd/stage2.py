@@ -254,6 +254,8 @@ def model_geometry(args):
     """feat_dim and noise-map size as main_denoiser.py:112-118 derives them from the (unloaded) ViT."""
     if args.model not in SPECS:
         raise NotImplementedError(f"{args.model}: only the DINOv2 S/B/L (+reg4) feature maps are supported")
+    from .vit import require_consumer_width
+    require_consumer_width(args.model, "stage-2 denoiser")
     spec = SPECS[args.model]
     return spec.dim, (args.input_size[0] - spec.patch) // args.stride_size + 1, \
         (args.input_size[1] - spec.patch) // args.stride_size + 1

@@ -87,6 +87,7 @@ def plan(args) -> dict:
         raise _lib.DvtError(f"--vit_checkpoint: {args.vit_checkpoint} does not exist")
     if args.fps < 1:
         raise _lib.DvtError(f"--fps {args.fps} must be positive")
+    _vit.require_consumer_width(args.model, "visualisation / video (DVT_VIS_MAX_C)")
     spec = _vit.SPECS[args.model]
     if args.height < spec.patch or args.width < spec.patch or args.stride_size < 1:
         raise _lib.DvtError(f"--height {args.height} --width {args.width} --stride_size {args.stride_size}: the frame must hold "

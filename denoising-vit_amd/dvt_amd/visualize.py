@@ -105,6 +105,8 @@ def load_image(path: str) -> torch.Tensor:
 
 # ---------------------------------------------------------------------------------------------------- the sweep
 def main(args, rank: int = 0, world: int = 1, device=None) -> int:
+    from .vit import require_consumer_width
+    require_consumer_width(args.model, "visualisation (DVT_VIS_MAX_C)")
     if device is None:
         device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
     torch.cuda.set_device(device)

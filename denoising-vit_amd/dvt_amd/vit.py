@@ -24,7 +24,10 @@ class VitConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "dim", "depth", "heads", "mlp_dim", "patch", "stride", "img_h", "img_w", "grid_h",
         "grid_w", "n_tokens", "s_pad", "k_patch", "n_prefix")] + [("ln_eps", C.c_float),
-                                                                  ("pos_has_cls", C.c_int32)]
+                                                                  ("pos_has_cls", C.c_int32), ("mlp_kind", C.c_int32)]
+
+
+MLP_GELU, MLP_SWIGLU = 0, 1  # DvtVitConfig.mlp_kind (include/dvt_vit.h)
 
 
 class VitBlockWeights(C.Structure):
@@ -42,6 +45,10 @@ _P, _I = C.c_void_p, C.c_int
 _lib.register_signatures({
     "dvt_vit_config": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(VitConfig)]),
     "dvt_vit_config_reg": (_I, [_I, _I, _I, _I, _I, _I, _I, C.POINTER(VitConfig)]),
+    "dvt_vit_config_ex": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(VitConfig)]),
+    "dvt_vit_gemm_swiglu": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "dvt_vit_swiglu_pack_index": (_I, [_I, _I]),
+    "dvt_vit_swiglu_act": (_I, [_P, _P, C.c_longlong, _I, _P]),
     "dvt_vit_workspace_bytes": (C.c_int64, [C.POINTER(VitConfig), _I]),
     "dvt_vit_struct_sizes": (_I, [C.POINTER(C.c_int64)]),
     "dvt_vit_forward": (_I, [C.POINTER(VitConfig), C.POINTER(VitWeights), _P, _P, _I, _I, _P, _P]),
@@ -82,10 +89,11 @@ class VitSpec:
     img_size: int = 518
     ls_init: float = 1e-5  # DINOv2 LayerScale init
     n_reg: int = 0         # register tokens (the *_reg4_* checkpoints; timm: no_embed_class=True)
+    mlp: str = "gelu"      # "gelu": fc2(GELU(fc1 x)), hidden 4 dim; "swiglu": timm SwiGLUPacked (ViT-g/14), hidden 4096
 
 
-# the DINOv2 ViT-S/B/L backbones of the reference's MODEL_LIST with and without register tokens
-# (vit_wrapper.py:21-30; BASELINE.json names B and L).  ViT-g uses a SwiGLU MLP: not built.
+# the DINOv2 ViT-S/B/L/g backbones of the reference's MODEL_LIST with and without register tokens
+# (vit_wrapper.py:21-30; BASELINE.json names B and L).  ViT-g/14: dim 1536, 40 blocks, 24 heads, SwiGLU MLP.
 SPECS = {
     "vit_small_patch14_dinov2.lvd142m": VitSpec(384, 12),
     "vit_base_patch14_dinov2.lvd142m": VitSpec(768, 12),
@@ -93,7 +101,52 @@ SPECS = {
     "vit_small_patch14_reg4_dinov2.lvd142m": VitSpec(384, 12, n_reg=4),
     "vit_base_patch14_reg4_dinov2.lvd142m": VitSpec(768, 12, n_reg=4),
     "vit_large_patch14_reg4_dinov2.lvd142m": VitSpec(1024, 24, n_reg=4),
+    "vit_giant_patch14_dinov2.lvd142m": VitSpec(1536, 40, mlp="swiglu"),
+    "vit_giant_patch14_reg4_dinov2.lvd142m": VitSpec(1536, 40, n_reg=4, mlp="swiglu"),
 }
+
+# Consumers of the extractor that hold a feature row in a fixed number of register slots (the per-image fit, the loss rows,
+# VisEngine, the video kernels, the stage-2 / stage-3 kernels): built for feature widths up to this
+MAX_CONSUMER_FEAT_DIM = 1024
+
+
+def require_consumer_width(model: str | None, consumer: str) -> None:
+    """Refuse, by name and before anything is written, a backbone whose features are wider than the consumers' kernels hold:
+    `consumer` names the driver (stage 1, evaluate, ...).  Models that are not in SPECS are left to the caller's own check."""
+    spec = SPECS.get(model)
+    if spec is not None and spec.dim > MAX_CONSUMER_FEAT_DIM:
+        raise _lib.DvtError(f"{model}: feat_dim {spec.dim} is wider than the feat_dim <= {MAX_CONSUMER_FEAT_DIM} the {consumer} "
+                            "kernels are built for (the extractor itself runs: dvt_amd.models.PretrainedViTWrapper); nothing "
+                            "was written")
+
+
+def swiglu_hidden(dim: int) -> int:
+    """Hidden width of timm's SwiGLUPacked / DINOv2's SwiGLU MLP at mlp_ratio 4: (int(dim * 4 * 2 / 3) + 7) // 8 * 8."""
+    return (int(dim * 4 * 2 / 3) + 7) // 8 * 8
+
+
+def swiglu_pack_index(n_hidden: int) -> torch.Tensor:
+    """Row permutation of the PACKED SwiGLU fc1 (include/dvt_vit.h, dvt_vit_gemm_swiglu): packed row p holds checkpoint row
+    index[p] of the [2 n_hidden, dim] weight (gates first, then values).  Of every 64 packed rows the first 32 are the gates of
+    hidden units [32 B, 32 B + 32), the last 32 the values of the same units, so one wave's 64-column accumulator block of the
+    GEMM holds gate and value of 32 units in the same lanes.  Pure host arithmetic (== dvt_vit_swiglu_pack_index)."""
+    if n_hidden <= 0 or n_hidden % 32:
+        raise _lib.DvtError(f"SwiGLU hidden width must be a positive multiple of 32, not {n_hidden}")
+    p = torch.arange(2 * n_hidden)
+    blk, q = p // 64, p % 64
+    return torch.where(q < 32, 32 * blk + q, n_hidden + 32 * blk + (q - 32))
+
+
+def swiglu_pack(t: torch.Tensor) -> torch.Tensor:
+    """Rows (dim 0: 2 n_hidden of them, gates then values) of a weight / bias / column-sum tensor in the packed order."""
+    return t[swiglu_pack_index(t.shape[0] // 2)]
+
+
+def swiglu_unpack(t: torch.Tensor) -> torch.Tensor:
+    """Inverse of swiglu_pack."""
+    out = torch.empty_like(t)
+    out[swiglu_pack_index(t.shape[0] // 2)] = t
+    return out
 
 
 def resample_pos_embed(pos_embed: torch.Tensor, new_grid: tuple[int, int], n_prefix_pos: int) -> torch.Tensor:
@@ -118,13 +171,19 @@ def resample_pos_embed(pos_embed: torch.Tensor, new_grid: tuple[int, int], n_pre
 
 
 def vit_config(dim: int, depth: int, patch: int, stride: int, img_h: int, img_w: int,
-               n_reg: int = 0, row_pad: int = 128) -> VitConfig:
+               n_reg: int = 0, row_pad: int = 128, mlp: str = "gelu") -> VitConfig:
     """`row_pad`: an image's tokens are padded to a multiple of it.  128 is what dvt_vit_config writes and what the fp32 /
     bf16x3 forwards need; the bf16 forward takes any multiple of 32 (round 6): 1370 tokens -> 1376 rows instead of 1408,
     2.3 % fewer rows through every GEMM and row-local kernel (DVT_VIT_ROW_PAD overrides, for A/B runs)."""
     cfg = VitConfig()
-    _lib.check(_lib.lib().dvt_vit_config_reg(dim, depth, patch, stride, img_h, img_w, n_reg, C.byref(cfg)),
-               "dvt_vit_config_reg")
+    if mlp == "gelu":
+        _lib.check(_lib.lib().dvt_vit_config_reg(dim, depth, patch, stride, img_h, img_w, n_reg, C.byref(cfg)),
+                   "dvt_vit_config_reg")
+    elif mlp == "swiglu":
+        _lib.check(_lib.lib().dvt_vit_config_ex(dim, depth, patch, stride, img_h, img_w, n_reg, MLP_SWIGLU, C.byref(cfg)),
+                   "dvt_vit_config_ex")
+    else:
+        raise _lib.DvtError(f"mlp must be 'gelu' or 'swiglu', not {mlp!r}")
     if row_pad != 128:
         if row_pad % 32 or row_pad <= 0:
             raise _lib.DvtError(f"row_pad must be a positive multiple of 32, not {row_pad}")
@@ -138,10 +197,15 @@ def vit_config(dim: int, depth: int, patch: int, stride: int, img_h: int, img_w:
 
 def random_state_dict(dim: int, depth: int, patch: int, n_tokens: int, seed: int = 0,
                       ls_gamma: float | None = 1e-5, well_conditioned: bool = False,
-                      n_reg: int = 0) -> dict:
+                      n_reg: int = 0, mlp: str = "gelu") -> dict:
     """Random-init weights in the timm layout (trunc_normal(0.02)-like matrices).  With
     `well_conditioned` biases / LayerScale / norm affine are random O(1) so that parity tests
-    exercise every term (LayerScale 1e-5 would hide block errors)."""
+    exercise every term (LayerScale 1e-5 would hide block errors).  mlp="swiglu": the SwiGLUPacked MLP of ViT-g/14
+    (fc1 [2 H, dim] gates first, fc2 [dim, H], H = swiglu_hidden(dim)); the default output is what it always was."""
+    if mlp not in ("gelu", "swiglu"):
+        raise _lib.DvtError(f"mlp must be 'gelu' or 'swiglu', not {mlp!r}")
+    hid = swiglu_hidden(dim) if mlp == "swiglu" else 4 * dim
+    fc1_n = 2 * hid if mlp == "swiglu" else hid
     g = torch.Generator().manual_seed(seed)
     rn = lambda *s, std=0.02: torch.randn(*s, generator=g) * std  # noqa: E731
     sd = {
@@ -164,14 +228,21 @@ def random_state_dict(dim: int, depth: int, patch: int, n_tokens: int, seed: int
         sd[p + "attn.qkv.bias"] = rn(3 * dim, std=0.2) if well_conditioned else torch.zeros(3 * dim)
         sd[p + "attn.proj.weight"] = rn(dim, dim, std=ws)
         sd[p + "attn.proj.bias"] = rn(dim, std=0.2) if well_conditioned else torch.zeros(dim)
-        sd[p + "mlp.fc1.weight"] = rn(4 * dim, dim, std=ws)
-        sd[p + "mlp.fc1.bias"] = rn(4 * dim, std=0.2) if well_conditioned else torch.zeros(4 * dim)
-        sd[p + "mlp.fc2.weight"] = rn(dim, 4 * dim, std=ws * 0.5)
+        sd[p + "mlp.fc1.weight"] = rn(fc1_n, dim, std=ws)
+        sd[p + "mlp.fc1.bias"] = rn(fc1_n, std=0.2) if well_conditioned else torch.zeros(fc1_n)
+        sd[p + "mlp.fc2.weight"] = rn(dim, hid, std=ws * 0.5)
         sd[p + "mlp.fc2.bias"] = rn(dim, std=0.2) if well_conditioned else torch.zeros(dim)
         for nm in ("ls1", "ls2"):
             sd[p + nm + ".gamma"] = (0.5 + torch.rand(dim, generator=g) if well_conditioned
                                      else torch.full((dim,), float(ls_gamma)))
     return sd
+
+
+def fold_layernorm(W: torch.Tensor, b: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor):
+    """LayerNorm folded into the consuming linear layer (include/dvt_vit.h): W' = bf16(gamma (.) W), its fp32 column sums
+    cs[n] = sum_k W'[n][k], and b' = b + W beta -- in fp32 from the checkpoint tensors.  Every output is row-local in W's rows."""
+    Wf = (W * gamma[None, :]).to(torch.bfloat16)
+    return Wf, Wf.float().sum(1), b + W @ beta
 
 
 _cap_warned: set = set()
@@ -197,7 +268,7 @@ _PLAN_CACHE: dict = {}
 
 
 def plan_launches(n_views: int, max_batch: int, s_pad: int = 1408, dim: int = 768, mlp_dim: int = 3072,
-                  fp32: bool = False) -> list[int]:
+                  fp32: bool = False, fc1_n: int | None = None) -> list[int]:
     """Views per extractor launch, TILE-ROUND aware (round 4).  Every GEMM of a launch runs (M / 256) x (N / 256) tiles of
     256 x 256 on 256 CUs, so its time is ceil(tiles / 256) ROUNDS: 110 views = 605 M panels give the N = 768 GEMMs (proj,
     fc2) 7.09 -> 8 rounds, 11 % of them idle, while 124 views (682 panels) give 23.98 / 31.97 / 7.99 / 7.99 rounds for qkv /
@@ -205,7 +276,7 @@ def plan_launches(n_views: int, max_batch: int, s_pad: int = 1408, dim: int = 76
     over a cost model in microseconds per tile round (k-loop 1.68 us per 64 k + the epilogue's 5.6 / 10.5 / 20 us: the
     measured 8p figures) plus the per-view kernels (attention, im2col): 769 views at a cap of 128 -> 124 x 5 + 103 + 46, at the
     default cap of 400 -> 398 + 371, modelled 4 % below 7 x 110.  Results do not depend on the split (tests).  DVT_VIT_BALANCE=1: equal launches (round 3),
-    0: plain chunks.
+    0: plain chunks.  `mlp_dim` is fc2's K; `fc1_n` fc1's N where it differs (SwiGLU: 2 mlp_dim), default mlp_dim.
     fp32 = True (round 5): the exact-fp32 extractor's GEMMs run 128 x 128 tiles, two workgroups per CU (512 slots per round,
     ~0.126 us per k and round at ~130 TF/s); at the round-4 cap of 32 views the N = 768 GEMMs ran 4.1 -> 5 rounds."""
     max_batch = max(1, int(max_batch))
@@ -213,19 +284,21 @@ def plan_launches(n_views: int, max_batch: int, s_pad: int = 1408, dim: int = 76
     if mode != "2":
         step = balanced_launch_views(n_views, max_batch)
         return [min(step, n_views - b0) for b0 in range(0, n_views, step)]
-    key = (n_views, max_batch, s_pad, dim, mlp_dim, fp32)
+    fc1_n = mlp_dim if fc1_n is None else fc1_n
+    key = (n_views, max_batch, s_pad, dim, mlp_dim, fp32, fc1_n)
     if key in _PLAN_CACHE:
         return list(_PLAN_CACHE[key])
     if fp32:
         tile, slots = 128, 512
         kt = lambda k: 0.126 * k  # noqa: E731
-        gemms = [(3 * dim // tile, kt(dim) + 2.0), (mlp_dim // tile, kt(dim) + 2.0), (dim // tile, kt(dim) + 2.0),
+        gemms = [(3 * dim // tile, kt(dim) + 2.0), (fc1_n // tile, kt(dim) + 2.0), (dim // tile, kt(dim) + 2.0),
                  (dim // tile, kt(mlp_dim) + 2.0)]
         per_view = 50.0 * (s_pad / 1408.0) ** 2 * (dim / 768.0)
     else:
         tile, slots = 256, 256
         kt = lambda k: 1.68 * (k / 64.0)  # noqa: E731
-        gemms = [(3 * dim // 256, kt(dim) + 5.6), (mlp_dim // 256, kt(dim) + 10.5), (dim // 256, kt(dim) + 20.0),
+        # (fc1's 10.5 us is the GELU epilogue's measured figure; the SwiGLU epilogue's own has not been measured)
+        gemms = [(3 * dim // 256, kt(dim) + 5.6), (fc1_n // 256, kt(dim) + 10.5), (dim // 256, kt(dim) + 20.0),
                  (dim // 256, kt(mlp_dim) + 10.0)]  # (N tiles, us per tile round): qkv, fc1, proj, fc2
         per_view = 8.8 * (s_pad / 1408.0) ** 2 * (dim / 768.0)  # attention + the row-local kernels
 
@@ -265,18 +338,30 @@ class HipViT:
         self.dtype = dtype
         self.x3 = matmul == "high"
         self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.DvtError("HipViT needs a HIP device; there is no CPU fallback")
         sd = {k: v.detach() for k, v in state_dict.items()}
         dim = sd["pos_embed"].shape[-1]
         depth = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("blocks."))
+        # SwiGLUPacked (ViT-g/14): fc1 carries gate and value rows, twice fc2's input width
+        fc1_n, fc2_k = sd["blocks.0.mlp.fc1.weight"].shape[0], sd["blocks.0.mlp.fc2.weight"].shape[1]
+        self.mlp = "swiglu" if fc1_n == 2 * fc2_k else "gelu"
+        if self.mlp == "gelu" and fc1_n != fc2_k:
+            raise _lib.DvtError(f"mlp.fc1 has {fc1_n} rows for an fc2 of {fc2_k} columns: neither a GELU nor a SwiGLU MLP")
+        if self.mlp == "swiglu" and self.x3:
+            raise _lib.DvtError(f"ViT with a SwiGLU MLP (dim {dim}, depth {depth}: the vit_giant_patch14 models): matmul=\"high\" "
+                                "(bf16x3) is built for the GELU MLP only; use matmul=\"highest\" or dtype=\"bfloat16\"")
+        if self.device.type != "cuda":
+            raise _lib.DvtError("HipViT needs a HIP device; there is no CPU fallback")
         n_reg = int(sd["reg_token"].shape[1]) if "reg_token" in sd else 0
         row_pad = 128  # (the bf16x3 forward: its split kernels walk 64-token blocks of whole 128-row images)
         if not self.x3:  # bf16 (round 6) and exact fp32 (round 6, second session): any multiple of 32 -- 1370 tokens -> 1376 rows
             env = os.environ.get("DVT_VIT_ROW_PAD", "")
             row_pad = int(env) if env.isdigit() and int(env) > 0 else 32
-        self.cfg = vit_config(dim, depth, patch, stride, img_size[0], img_size[1], n_reg, row_pad=row_pad)
+        self.cfg = vit_config(dim, depth, patch, stride, img_size[0], img_size[1], n_reg, row_pad=row_pad, mlp=self.mlp)
         cfg = self.cfg
+        if self.mlp == "swiglu" and fc2_k != cfg.mlp_dim:
+            raise _lib.DvtError(f"SwiGLU hidden width {fc2_k} is not the {cfg.mlp_dim} of dim {dim}")
+        # bf16 path: fc1's rows (weight, bias, fold terms) go to the device in the packed order the SwiGLU epilogue pairs
+        pack = swiglu_pack if (self.mlp == "swiglu" and dtype == "bfloat16") else (lambda t: t)
         # other strides / input sizes: the checkpoint's position grid is resampled once, on the host
         sd["pos_embed"] = resample_pos_embed(sd["pos_embed"], (cfg.grid_h, cfg.grid_w), int(cfg.pos_has_cls))
         if sd["pos_embed"].shape[1] != cfg.pos_has_cls + cfg.grid_h * cfg.grid_w:
@@ -320,7 +405,7 @@ class HipViT:
             b.proj_w, b.proj_b = bf16(sd[p + "attn.proj.weight"]), f32(sd[p + "attn.proj.bias"])
             b.ls1 = f32(sd.get(p + "ls1.gamma", torch.ones(dim)))
             b.norm2_w, b.norm2_b = f32(sd[p + "norm2.weight"]), f32(sd[p + "norm2.bias"])
-            b.fc1_w, b.fc1_b = bf16(sd[p + "mlp.fc1.weight"]), f32(sd[p + "mlp.fc1.bias"])
+            b.fc1_w, b.fc1_b = bf16(pack(sd[p + "mlp.fc1.weight"])), f32(pack(sd[p + "mlp.fc1.bias"]))
             b.fc2_w, b.fc2_b = bf16(sd[p + "mlp.fc2.weight"]), f32(sd[p + "mlp.fc2.bias"])
             b.ls2 = f32(sd.get(p + "ls2.gamma", torch.ones(dim)))
             if dtype == "bfloat16":
@@ -329,10 +414,12 @@ class HipViT:
                 for norm, lin, dst in (("norm1", "attn.qkv", "qkv"), ("norm2", "mlp.fc1", "fc1")):
                     W = sd[p + lin + ".weight"].float()
                     gamma, beta = sd[p + norm + ".weight"].float(), sd[p + norm + ".bias"].float()
-                    Wf = (W * gamma[None, :]).to(torch.bfloat16)
+                    Wf, cs, bf = fold_layernorm(W, sd[p + lin + ".bias"].float(), gamma, beta)
+                    if dst == "fc1":  # (SwiGLU: a row permutation of all three -- the fold is row-local)
+                        Wf, cs, bf = pack(Wf), pack(cs), pack(bf)
                     setattr(b, dst + "_wf", bf16(Wf))
-                    setattr(b, dst + "_cs", f32(Wf.float().sum(1)))
-                    setattr(b, dst + "_bf", f32(sd[p + lin + ".bias"].float() + W @ beta))
+                    setattr(b, dst + "_cs", f32(cs))
+                    setattr(b, dst + "_bf", f32(bf))
         self.weights = w
         self._ws = None
         self._ws_batch = 0
@@ -411,12 +498,13 @@ class HipViT:
     def launch_plan(self, n_views: int, max_batch: int = 128) -> list[int]:
         """Views of each extractor launch for `n_views` views (what forward_features will do)."""
         cfg = self.cfg
+        fc1_n = 2 * cfg.mlp_dim if self.mlp == "swiglu" else cfg.mlp_dim  # fc1's true N (SwiGLU: gates + values)
         max_batch = self._memory_cap(max_batch if not (self.dtype == "float32" and not self.x3) else min(max_batch, 160))
         if self.dtype == "float32" and self.x3:
             max_batch = min(max_batch, 64)  # bf16x3: 64 views, 4.4 GB of scratch
         elif self.dtype == "float32":
             # exact fp32: 51 MB of scratch per ViT-B view; launches of up to 160 views (8 GB) so that the 128 x 128 tiles of
             # the N = dim GEMMs fill whole rounds of 512 workgroup slots (round 4: 32 views, 4.1 -> 5 rounds, 18 % idle)
-            return plan_launches(n_views, min(max_batch, 160), cfg.s_pad, cfg.dim, cfg.mlp_dim, fp32=True)
-        return plan_launches(n_views, max_batch, cfg.s_pad, cfg.dim, cfg.mlp_dim)
+            return plan_launches(n_views, min(max_batch, 160), cfg.s_pad, cfg.dim, cfg.mlp_dim, fp32=True, fc1_n=fc1_n)
+        return plan_launches(n_views, max_batch, cfg.s_pad, cfg.dim, cfg.mlp_dim, fc1_n=fc1_n)
 

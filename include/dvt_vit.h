@@ -28,10 +28,10 @@ extern "C" {
 #define DVT_VIT_MAX_DEPTH 48
 
 typedef struct DvtVitConfig {
-  int32_t dim;       /* 768 (B) / 1024 (L); multiple of 128 */
+  int32_t dim;       /* 384 (S) / 768 (B) / 1024 (L) / 1536 (g); multiple of 128, at most 1536 */
   int32_t depth;     /* 12 / 24 */
   int32_t heads;     /* dim / 64: head_dim is fixed to 64 */
-  int32_t mlp_dim;   /* 4 * dim */
+  int32_t mlp_dim;   /* K of fc2: 4 * dim (GELU MLP); 4096 for the SwiGLU MLP of ViT-g (fc1's N is then 2 * mlp_dim) */
   int32_t patch;     /* 14 */
   int32_t stride;    /* conv stride (14; the reference's --stride_size) */
   int32_t img_h, img_w; /* 518 x 518 */
@@ -45,7 +45,12 @@ typedef struct DvtVitConfig {
   float ln_eps;      /* 1e-6 */
   int32_t pos_has_cls; /* 1: pos_embed[0] belongs to cls, patches follow (DINOv2); 0: pos_embed covers
                         * the patch tokens only (timm no_embed_class=True, the reg4 models) */
+  int32_t mlp_kind;  /* DVT_VIT_MLP_GELU (0): fc2(GELU(fc1 x)); DVT_VIT_MLP_SWIGLU (1): timm SwiGLUPacked with SiLU (ViT-g/14),
+                      * h = fc1 x [2 * mlp_dim], y = fc2(silu(h[:mlp_dim]) * h[mlp_dim:]).  A zero-initialised config is a GELU one. */
 } DvtVitConfig;
+
+#define DVT_VIT_MLP_GELU 0
+#define DVT_VIT_MLP_SWIGLU 1
 
 /* All matrices bf16 row-major [out, in] (nn.Linear layout), vectors fp32. */
 typedef struct DvtVitBlockWeights {
@@ -54,7 +59,8 @@ typedef struct DvtVitBlockWeights {
   const void* proj_w; const float* proj_b;  /* [dim, dim] */
   const float* ls1;                         /* LayerScale gamma [dim] */
   const float* norm2_w; const float* norm2_b;
-  const void* fc1_w;  const float* fc1_b;   /* [mlp_dim, dim] */
+  const void* fc1_w;  const float* fc1_b;   /* [mlp_dim, dim]; SwiGLU: [2 * mlp_dim, dim], gate rows first (the checkpoint's order) for
+                                             * the fp32 forward, rows in the PACKED order of dvt_vit_swiglu_pack_index for the bf16 one */
   const void* fc2_w;  const float* fc2_b;   /* [dim, mlp_dim] */
   const float* ls2;
   /* Optional (bf16 path; all six or none): LayerNorm folded into the GEMMs.  With W' = bf16(norm.weight (.) W)
@@ -79,6 +85,10 @@ int dvt_vit_config(int dim, int depth, int patch, int stride, int img_h, int img
 /* Same with register tokens (vit_wrapper.py:27-30, the *_reg4_dinov2 models: n_reg_tokens = 4). */
 int dvt_vit_config_reg(int dim, int depth, int patch, int stride, int img_h, int img_w,
                        int n_reg_tokens, DvtVitConfig* h_out);
+/* The same with the MLP kind (DVT_VIT_MLP_*).  mlp_kind 0 writes what dvt_vit_config_reg writes; DVT_VIT_MLP_SWIGLU sets
+ * mlp_dim = (int(dim * 4 * 2 / 3) + 7) / 8 * 8 (the hidden width of timm's / DINOv2's SwiGLU MLP at mlp_ratio 4: 4096 for 1536). */
+int dvt_vit_config_ex(int dim, int depth, int patch, int stride, int img_h, int img_w, int n_reg_tokens, int mlp_kind,
+                      DvtVitConfig* h_out);
 /* HOST: bytes of scratch needed for a forward of `batch` images. */
 int64_t dvt_vit_workspace_bytes(const DvtVitConfig* h_cfg, int batch);
 int dvt_vit_struct_sizes(int64_t* h_out3); /* {DvtVitConfig, DvtVitBlockWeights, DvtVitWeights} */
@@ -138,6 +148,7 @@ int dvt_vit_attention_x3_presplit(const void* scratch, void* out, int batch, int
 int64_t dvt_vit_workspace_bytes_f32x3(const DvtVitConfig* h_cfg, int batch);
 int dvt_vit_forward_f32x3(const DvtVitConfig* h_cfg, const DvtVitWeights* h_w, const float* img, float* feat,
                           int batch, int n_blocks, void* workspace, void* stream);
+/* (The bf16x3 forward and its workspace function take GELU configs only: mlp_kind = DVT_VIT_MLP_SWIGLU is DVT_E_BADARG / -1.) */
 /* fp32 attention on qkv [batch*s_pad, 3*heads*64] (q | k | v, head-major inside): out [batch*s_pad, heads*64].  s_pad % 32 == 0
  * (round 6); blocks of 128 queries: where s_pad is not a multiple of 128 the kernel READS up to 96 rows behind an image's rows of
  * qkv as queries (the next image's, or whatever lies behind the last one: nothing of them is stored -- the caller keeps those
@@ -154,6 +165,24 @@ int dvt_vit_gemm_bias(const void* x, const void* w, const float* b, void* y, int
  * or 4, the default) for the folded form; DVT_E_BADARG otherwise. */
 int dvt_vit_gemm_lnfold(const void* x, const void* w, const float* b, void* y, int m, int n, int k,
                         const void* ln_stats, const float* ln_cs, int gelu, void* stream);
+/* The SwiGLU fc1 GEMM as the extractor launches it for ViT-g: y[m, j] (bf16, [m, n_hidden]) = silu(g_j) * v_j with
+ * g_j = x[m, :] . W[j, :] + b[j] (gate) and v_j = x[m, :] . W[n_hidden + j, :] + b[n_hidden + j] (value); the full-width
+ * [m, 2 n_hidden] product is never written.  `w_packed` [2 n_hidden, k], `b_packed` [2 n_hidden] (and `ln_cs`) hold the rows in
+ * the PACKED order: packed row p holds checkpoint row dvt_vit_swiglu_pack_index(p, n_hidden) -- of every 64 packed rows the
+ * first 32 are the gates of hidden units [32 B, 32 B + 32), the last 32 the values of the same units (B = p / 64), so that a
+ * wave's 64-column accumulator block holds both halves of 32 products in the same lanes.  ln_stats / ln_cs non-NULL: the
+ * LayerNorm folded as in dvt_vit_gemm_lnfold, applied to gate and value before the product (needs a 256-row schedule, 3 or
+ * 4, and m % 256 == 0; DVT_E_BADARG otherwise, nothing written).  m % 128 == n_hidden % 64 == k % 64 == 0.
+ * silu(g) = g / (1 + 2^(-g log2 e)) with the exponent clamped at 126: finite for every finite g. */
+int dvt_vit_gemm_swiglu(const void* x, const void* w_packed, const float* b_packed, void* y, int m, int n_hidden, int k,
+                        const void* ln_stats, const float* ln_cs, void* stream);
+/* The UNFUSED form of that epilogue, kept for A/B measurements (tools/bench_vitg.py; the extractor does not launch it):
+ * hid [m, n_hidden] (bf16) = silu(h[:, :n_hidden]) * h[:, n_hidden:] of a full-width h [m, 2 n_hidden] (bf16, checkpoint column
+ * order), e.g. what dvt_vit_gemm_bias writes from UNPACKED weights.  n_hidden % 8 == 0. */
+int dvt_vit_swiglu_act(const void* h, void* hid, long long m, int n_hidden, void* stream);
+/* HOST: checkpoint row (0 .. 2 n_hidden - 1: gates, then values) that packed row p holds; -1 for bad arguments
+ * (n_hidden % 32 != 0, p out of range). */
+int dvt_vit_swiglu_pack_index(int p, int n_hidden);
 /* x[m, n] (fp32, in place) += gamma[n] * (a[m, k] (bf16) . w[n, k]^T (bf16) + b[n]): the attention-proj /
  * fc2 GEMM with the LayerScale + residual epilogue (timm Block.forward: x = x + ls(f(norm(x)))) */
 int dvt_vit_gemm_residual(const void* a, const void* w, const float* b, const float* gamma, float* x,
@@ -166,7 +195,7 @@ int dvt_vit_gemm_residual(const void* a, const void* w, const float* b, const fl
 int dvt_vit_gemm_residual_stats(const void* a, const void* w, const float* b, const float* gamma, float* x, void* xb,
                                 void* stats, void* part_scratch, int m, int n, int k, float eps, void* stream);
 /* xb (bf16 [rows, dim]) = bf16(x fp32 [rows, dim]) and stats[rows] (float2) = (mean, rstd) in two passes: what the folded
- * forward runs behind the patch embedding.  dim % 4 == 0, dim <= 1024. */
+ * forward runs behind the patch embedding.  dim % 4 == 0, dim <= 1536. */
 int dvt_vit_ln_cast_stats(const float* x, void* xb, void* stats, int rows, int dim, float eps, void* stream);
 /* The qkv GEMM of dvt_vit_forward: x bf16 [m, dim] . w^T (bf16 [3 dim, dim]) + b, q columns times q_scale (0: as they are),
  * q | k into qk bf16 [m, 2 dim], v TRANSPOSED per head into vt bf16 [batch, heads, 64, s_pad] (the layout dvt_vit_attention
@@ -175,7 +204,7 @@ int dvt_vit_ln_cast_stats(const float* x, void* xb, void* stats, int rows, int d
  * folded as in dvt_vit_gemm_lnfold (w, b the folded weights); needs 3 dim % 256 == 0 and a 256-row schedule (3 or 4). */
 int dvt_vit_gemm_qkv(const void* x, const void* w, const float* b, void* qk, void* vt, int m, int dim, int heads, int s_pad,
                      int batch, const void* ln_stats, const float* ln_cs, float q_scale, void* stream);
-/* y (bf16) [rows, dim] = LayerNorm(x fp32 [rows, dim]) * w + b */
+/* y (bf16) [rows, dim] = LayerNorm(x fp32 [rows, dim]) * w + b; dim % 4 == 0, dim <= 1536 */
 int dvt_vit_layernorm(const float* x, const float* w, const float* b, void* y, int rows, int dim,
                       float eps, void* stream);
 /* s_pad % 16 == 0.  out[b, s, h*64 + d] (bf16, [batch*s_pad, heads*64]) = softmax(q k^T / 8) v over the first
