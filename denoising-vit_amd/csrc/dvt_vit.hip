@@ -2542,6 +2542,21 @@ void launch_final_norm(const float* x, const float* w, const float* b, float* y,
                        dim, eps, s_pad, n_tokens, n_prefix);
 }
 
+// im2col of `rows` token rows (rows >= real_rows = batch * s_pad: the phantom rows behind the last image are zero-filled).
+// The pair kernel where the patch size is one of its instantiations (14: DINOv2; 16, 8: DINO / DeiT-III / AugReg) and the
+// geometry is even, else the generic kernel.
+void launch_im2col(const DvtVitConfig* c, const float* img, bf16_t* col, int rows, int real_rows, hipStream_t s) {
+  const bool even = c->stride % 2 == 0 && c->img_w % 2 == 0 && c->k_patch % 2 == 0;
+  if (even && c->patch == 14)
+    hipLaunchKernelGGL(im2col_pairs_kernel<14>, dim3(rows), dim3(256), 0, s, img, col, *c, real_rows);
+  else if (even && c->patch == 16)
+    hipLaunchKernelGGL(im2col_pairs_kernel<16>, dim3(rows), dim3(256), 0, s, img, col, *c, real_rows);
+  else if (even && c->patch == 8)
+    hipLaunchKernelGGL(im2col_pairs_kernel<8>, dim3(rows), dim3(256), 0, s, img, col, *c, real_rows);
+  else
+    hipLaunchKernelGGL(im2col_kernel, dim3(rows), dim3(256), 0, s, img, col, *c, real_rows);
+}
+
 int check_vit_cfg(const DvtVitConfig* c) {
   if (!c || c->dim <= 0 || c->dim % 128 || c->dim > 1536 || c->heads * 64 != c->dim) return DVT_E_BADARG;
   if (c->depth < 1 || c->depth > DVT_VIT_MAX_DEPTH || c->mlp_dim <= 0 || c->mlp_dim % 128) return DVT_E_BADARG;
@@ -2708,6 +2723,17 @@ extern "C" int dvt_vit_config_ex(int dim, int depth, int patch, int stride, int 
   c->k_patch = (3 * patch * patch + 63) / 64 * 64;
   c->ln_eps = 1e-6f;
   return check_vit_cfg(c);
+}
+
+// The forward's im2col alone: col bf16 [batch * s_pad, k_patch]
+extern "C" int dvt_vit_im2col(const DvtVitConfig* c, const float* img, void* col, int batch, void* stream) {
+  const int rc = check_vit_cfg(c);
+  if (rc) return rc;
+  if (!img || !col || batch <= 0 || c->patch <= 0 || c->stride <= 0 || 3 * c->patch * c->patch > c->k_patch) return DVT_E_BADARG;
+  if ((c->grid_h - 1) * c->stride + c->patch > c->img_h || (c->grid_w - 1) * c->stride + c->patch > c->img_w) return DVT_E_BADARG;
+  launch_im2col(c, img, (bf16_t*)col, batch * c->s_pad, batch * c->s_pad, (hipStream_t)stream);
+  DVT_CHECK_LAUNCH();
+  return 0;
 }
 
 extern "C" int64_t dvt_vit_workspace_bytes(const DvtVitConfig* c, int batch) {
@@ -3079,12 +3105,7 @@ extern "C" int dvt_vit_forward(const DvtVitConfig* c, const DvtVitWeights* w, co
   } while (0)
 
   // patch embedding: im2col -> GEMM with the (+bias, +pos_embed, cls) epilogue
-  if (c->patch == 14 && c->stride % 2 == 0 && c->img_w % 2 == 0 && c->k_patch % 2 == 0)
-    hipLaunchKernelGGL(im2col_pairs_kernel<14>, dim3(T), dim3(256), 0, s, img, k.col, *c, batch * c->s_pad);
-  else if (c->patch == 16 && c->stride % 2 == 0 && c->img_w % 2 == 0 && c->k_patch % 2 == 0)
-    hipLaunchKernelGGL(im2col_pairs_kernel<16>, dim3(T), dim3(256), 0, s, img, k.col, *c, batch * c->s_pad);
-  else
-    hipLaunchKernelGGL(im2col_kernel, dim3(T), dim3(256), 0, s, img, k.col, *c, batch * c->s_pad);
+  launch_im2col(c, img, k.col, T, batch * c->s_pad, s);
   DVT_CHECK_LAUNCH();
   {
     GemmBArgs a{};

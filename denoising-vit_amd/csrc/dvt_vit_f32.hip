@@ -557,6 +557,17 @@ extern "C" int dvt_vit_attention_f32(const float* qkv, float* out, int batch, in
   return 0;
 }
 
+// The fp32 forward's im2col alone: col fp32 [batch * s_pad, k_patch]
+extern "C" int dvt_vit_im2col_f32(const DvtVitConfig* c, const float* img, float* col, int batch, void* stream) {
+  if (!c || !img || !col || batch <= 0 || c->s_pad <= 0 || c->s_pad < c->n_tokens || c->n_prefix < 1) return DVT_E_BADARG;
+  if (c->patch <= 0 || c->stride <= 0 || c->grid_h <= 0 || c->grid_w <= 0 || 3 * c->patch * c->patch > c->k_patch) return DVT_E_BADARG;
+  if (c->n_tokens != c->n_prefix + c->grid_h * c->grid_w) return DVT_E_BADARG;
+  if ((c->grid_h - 1) * c->stride + c->patch > c->img_h || (c->grid_w - 1) * c->stride + c->patch > c->img_w) return DVT_E_BADARG;
+  hipLaunchKernelGGL(im2col_f32_kernel, dim3(batch * c->s_pad), dim3(256), 0, (hipStream_t)stream, img, col, *c);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int dvt_vit_forward_f32(const DvtVitConfig* c, const DvtVitWeights* w, const float* img, float* feat,
                                    int batch, int n_blocks, void* workspace, void* stream) {
   if (!c || !w || !img || !feat || !workspace || batch <= 0 || n_blocks < 0 || n_blocks > c->depth)

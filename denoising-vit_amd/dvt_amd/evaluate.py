@@ -469,8 +469,11 @@ def metrics_table(met: dict, classes) -> str:
 def main(argv=None) -> dict:
     args = get_args(argv)
     # the probe heads' kernels have only been built and measured for the S / B / L widths: a wider backbone stops here, by name
-    from .vit import require_consumer_width
+    from .vit import require_consumer_width, require_dinov2_layout
     require_consumer_width(args.backbone_type, "linear-probe evaluation")
+    # ... and their data path pads to multiples of 14, normalises with ImageNet's statistics and sizes the denoiser for 37 x 37
+    require_dinov2_layout(args.backbone_type, "linear-probe evaluation",
+                          "its data path pads to the patch-14 grid and normalises with ImageNet's statistics")
     if args.task == "depth":
         return main_depth(args)
     opts = (args.cfg_options or []) + (args.options or [])

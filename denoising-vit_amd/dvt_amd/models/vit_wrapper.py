@@ -11,11 +11,12 @@ Differences forced by the environment (documented in DESIGN.md):
     does when the pretrained weights cannot be loaded -- features of a random ViT written to
     disk would be skipped forever by the existence-based resume.  Random init (seed 0) is
     available only on request (`allow_random_init=True`: synthetic benchmarks and tests).
-  * only the DINOv2 S/B/L/g backbones (with / without registers) are built; the other ids of
-    the reference's MODEL_LIST raise NotImplementedError (out of scope).  ViT-g/14
+  * the DINOv2 S/B/L/g backbones (with / without registers), the four DINO patch-8 / patch-16 models, DeiT-III B/16
+    and AugReg B/16-384 are built (dvt_amd.vit.SPECS); the MAE, CLIP and EVA-02 ids of the reference's MODEL_LIST raise
+    NotImplementedError with the reason (dvt_amd.vit.NOT_BUILT).  ViT-g/14
     (dim 1536, 40 blocks, SwiGLU MLP) runs in bfloat16 and exact float32; matmul="high" is refused.
   * the stride override (vit_wrapper.py:78-91) is honoured by the im2col kernel, but a
-    grid other than the checkpoint's 37x37 is served by resampling pos_embed on the host (timm's
+    grid other than the checkpoint's own is served by resampling pos_embed on the host (timm's
     resample_abs_pos_embed restated); the *_reg4_* models carry 4 register tokens (prefix tokens
     are stripped from the returned map like timm's `return_prefix_tokens=False`).
 """
@@ -53,7 +54,7 @@ MODEL_LIST = [
     "vit_base_patch16_384.augreg_in21k_ft_in1k",
 ]  # entry for entry the reference's list (dvt/models/vit_wrapper.py:15-56; its SAM / I-JEPA ids are commented out)
 
-IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+IMAGENET_MEAN, IMAGENET_STD = _vit.IMAGENET_MEAN, _vit.IMAGENET_STD
 
 
 class Normalize:
@@ -117,8 +118,10 @@ class PretrainedViTWrapper(nn.Module):
         super().__init__()
         assert model_identifier in MODEL_LIST, f"Model type {model_identifier} not tested yet."
         if model_identifier not in _vit.SPECS:
+            why = _vit.NOT_BUILT.get(model_identifier)
             raise NotImplementedError(
-                f"{model_identifier}: only {sorted(_vit.SPECS)} are built for MI355X (BASELINE.json)")
+                f"{model_identifier}: only {sorted(_vit.SPECS)} are built for MI355X (BASELINE.json)"
+                + (f" -- {why}" if why else ""))
         self.model_identifier = model_identifier
         self.stride = stride
         self.patch_size = int(re.search(r"patch(\d+)", model_identifier).group(1))
@@ -139,7 +142,7 @@ class PretrainedViTWrapper(nn.Module):
 
     def create_model(self, model_identifier: str, checkpoint_path: str | None = None):
         path = checkpoint_path or os.environ.get("DVT_VIT_CHECKPOINT")
-        n_tokens = (0 if self.spec.n_reg else 1) + (self.spec.img_size // self.spec.patch) ** 2
+        n_tokens = self.spec.n_pos  # rows of the position table: the checkpoint's grid, with or without a cls row
         if path:
             sd = torch.load(path, map_location="cpu")
             sd = sd.get("state_dict", sd.get("model", sd))
@@ -157,9 +160,10 @@ class PretrainedViTWrapper(nn.Module):
             # O(1) LayerScale / biases / norm affines: with DINOv2's LayerScale init (1e-5) twelve
             # random blocks would be a numerical no-op and neither parity nor power draw would mean much
             sd = _vit.random_state_dict(self.spec.dim, self.spec.depth, self.spec.patch, n_tokens,
-                                        seed=0, well_conditioned=True, n_reg=self.spec.n_reg, mlp=self.spec.mlp)
-        # timm data config of the DINOv2 models: ImageNet mean/std
-        return sd, Compose([Normalize(IMAGENET_MEAN, IMAGENET_STD)])
+                                        seed=0, well_conditioned=True, n_reg=self.spec.n_reg, mlp=self.spec.mlp,
+                                        layer_scale=self.spec.layer_scale)
+        # timm data config of the model: ImageNet mean / std, 0.5 / 0.5 for AugReg
+        return sd, Compose([Normalize(self.spec.mean, self.spec.std)])
 
     @property
     def n_output_dims(self) -> int:
@@ -180,7 +184,7 @@ class PretrainedViTWrapper(nn.Module):
         key = (torch.device(device), dtype, matmul)
         if key not in self._hip:
             self._hip[key] = _vit.HipViT(self._state_dict, self.patch_size, self.stride, self.img_size,
-                                         device, dtype=dtype, matmul=matmul)
+                                         device, dtype=dtype, matmul=matmul, pos_has_cls=self.spec.pos_has_cls)
         return self._hip[key]
 
     def features_nhwc(self, x: torch.Tensor, layer_index: int | None = None,

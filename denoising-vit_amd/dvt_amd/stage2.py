@@ -242,7 +242,7 @@ def get_args(argv=None):
     elif len(args.input_size) == 1:
         args.input_size = (args.input_size[0], args.input_size[0])
     if args.auto_stride:
-        args.stride_size = int(re.search(r"patch(14|16)", args.model).group(1))
+        args.stride_size = int(re.search(r"patch(\d+)", args.model).group(1))
     if args.stride_size in (8, 16) and args.input_size[0] == 518:
         args.input_size = (512, 512)
     if args.input_size[0] % args.stride_size or args.input_size[1] % args.stride_size:
@@ -253,7 +253,7 @@ def get_args(argv=None):
 def model_geometry(args):
     """feat_dim and noise-map size as main_denoiser.py:112-118 derives them from the (unloaded) ViT."""
     if args.model not in SPECS:
-        raise NotImplementedError(f"{args.model}: only the DINOv2 S/B/L (+reg4) feature maps are supported")
+        raise NotImplementedError(f"{args.model}: only the feature maps of {sorted(SPECS)} are supported")
     from .vit import require_consumer_width
     require_consumer_width(args.model, "stage-2 denoiser")
     spec = SPECS[args.model]

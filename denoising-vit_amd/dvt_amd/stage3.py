@@ -44,7 +44,7 @@ from . import dist as D
 from .models.vit_wrapper import IMAGENET_MEAN, IMAGENET_STD, MODEL_LIST
 from .stage2 import CosineScheduler, sampler_indices
 from .utils import misc
-from .vit import SPECS
+from .vit import SPECS, model_statistics, require_dinov2_layout
 
 # torchvision.datasets.folder.IMG_EXTENSIONS
 IMG_EXTENSIONS = (".jpg", ".jpeg", ".png", ".ppm", ".bmp", ".pgm", ".tif", ".tiff", ".webp")
@@ -79,9 +79,9 @@ def flip_decision(seed: int, step: int, position: int) -> bool:
     return bool(np.random.default_rng((seed, step, position)).random() < 0.5)
 
 
-def load_image(path: str, size: tuple, flip: bool) -> np.ndarray:
+def load_image(path: str, size: tuple, flip: bool, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> np.ndarray:
     """main_distillation.py's transform: PIL decode -> RGB -> Resize(size, BICUBIC, antialias) -> flip -> ToTensor ->
-    ImageNet Normalize; -> fp32 [3, H, W]."""
+    Normalize with the model's statistics (`model_statistics`); -> fp32 [3, H, W]."""
     from PIL import Image
     with open(path, "rb") as f:
         img = Image.open(f).convert("RGB")
@@ -90,7 +90,7 @@ def load_image(path: str, size: tuple, flip: bool) -> np.ndarray:
     if flip:
         img = img.transpose(Image.FLIP_LEFT_RIGHT)
     a = np.asarray(img, dtype=np.float32) / 255.0
-    a = (a - np.asarray(IMAGENET_MEAN, np.float32)) / np.asarray(IMAGENET_STD, np.float32)
+    a = (a - np.asarray(mean, np.float32)) / np.asarray(std, np.float32)
     return np.ascontiguousarray(a.transpose(2, 0, 1))
 
 
@@ -100,8 +100,9 @@ class ImageFeeder:
     stream waits for."""
 
     def __init__(self, ds: ImageFolderList, indices, batch_size, size, device, seed, first_step, rank,
-                 workers=8, depth=2):
+                 workers=8, depth=2, mean=IMAGENET_MEAN, std=IMAGENET_STD):
         self.ds, self.it, self.bs, self.size, self.device = ds, indices, batch_size, tuple(size), device
+        self.mean, self.std = tuple(mean), tuple(std)
         self.seed, self.step, self.rank = seed, first_step, rank
         self.pool = ThreadPoolExecutor(max(1, workers))
         cuda = device.type == "cuda"
@@ -119,7 +120,7 @@ class ImageFeeder:
 
     def _load_one(self, slot, step, j, index):
         flip = flip_decision(self.seed, step, self.rank * self.bs + j)
-        self.host[slot][j].copy_(torch.from_numpy(load_image(self.ds.samples[index][0], self.size, flip)))
+        self.host[slot][j].copy_(torch.from_numpy(load_image(self.ds.samples[index][0], self.size, flip, self.mean, self.std)))
 
     def _run(self):
         try:
@@ -253,7 +254,7 @@ def get_args(argv=None):
         raise SystemExit("--input_size takes two values (H W)")
     args.input_size = tuple(args.input_size)
     if args.auto_stride:
-        args.stride_size = int(re.search(r"patch(14|16)", args.model).group(1))
+        args.stride_size = int(re.search(r"patch(\d+)", args.model).group(1))
     if args.stride_size in (8, 16) and args.input_size[0] == 518:
         args.input_size = (512, 512)
     if args.input_size[0] % args.stride_size or args.input_size[1] % args.stride_size:
@@ -264,7 +265,10 @@ def get_args(argv=None):
 def geometry(args):
     """(dim, depth, patch, grid_h, grid_w, n_reg) of the student at this input size and stride."""
     if args.model not in SPECS:
-        raise NotImplementedError(f"{args.model}: only the DINOv2 S/B/L (+reg4) ViTs are built")
+        raise NotImplementedError(f"{args.model}: the stage-3 trainer takes the DINOv2 S/B/L (+reg4) ViTs of dvt_amd.vit.SPECS only")
+    # the trainer's parameter arena holds LayerScale as trained tensors and derives the position table's cls row from the
+    # registers: the DINO / AugReg (no LayerScale) and DeiT-III (no cls row, no registers) layouts stop here, by name
+    require_dinov2_layout(args.model, "the stage-3 trainer", "its parameter arena trains ls1 / ls2 and a DINOv2 position table")
     s = SPECS[args.model]
     return (s.dim, s.depth, s.patch, (args.input_size[0] - s.patch) // args.stride_size + 1,
             (args.input_size[1] - s.patch) // args.stride_size + 1, s.n_reg)
@@ -307,6 +311,9 @@ def train(args, rank: int, world: int, device: torch.device, model_factory=None)
     """The loop of main_distillation.py:218-296.  `model_factory(args, device) -> (student engine, teacher)` lets the CPU
     tests inject stand-ins with the engine interface (the product engine needs a HIP device)."""
     distributed = world > 1
+    if model_factory is None:
+        geometry(args)  # a model the trainer is not built for stops here, before the run directory exists
+    mean, std = model_statistics(args.model)
     log_dir = os.path.join(args.output_root, args.project, args.run_name)
     if rank == 0:
         os.makedirs(f"{log_dir}/checkpoints", exist_ok=True)
@@ -323,7 +330,7 @@ def train(args, rank: int, world: int, device: torch.device, model_factory=None)
     lr_base = learning_rate(args, world)
     sched = scheduler(args, lr_base, n_iter)
     feeder = ImageFeeder(ds, sampler_indices(len(ds), world, rank, distributed), args.batch_size, args.input_size, device,
-                         args.seed, 0, rank, workers=args.num_workers)
+                         args.seed, 0, rank, workers=args.num_workers, mean=mean, std=std)
     micro = args.micro_batch if args.micro_batch > 0 else None
     history, t_log = [], time.time()
     pending = []

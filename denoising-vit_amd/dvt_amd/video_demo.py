@@ -26,7 +26,8 @@ from . import _lib
 from . import video as VD
 from . import vit as _vit
 
-IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+IMAGENET_MEAN, IMAGENET_STD = _vit.IMAGENET_MEAN, _vit.IMAGENET_STD
+model_statistics = _vit.model_statistics
 
 
 def get_args(argv=None):
@@ -63,15 +64,15 @@ def scene_name(directory: str) -> str:
     return os.path.basename(os.path.normpath(directory))
 
 
-def load_frame(path: str, height: int, width: int) -> torch.Tensor:
+def load_frame(path: str, height: int, width: int, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> torch.Tensor:
     """The script's base_transform on the host: RGB, PIL bicubic resize to (width, height), ToTensor, the model's
-    normalisation.  float32 [3, height, width]."""
+    normalisation (`model_statistics`).  float32 [3, height, width]."""
     from PIL import Image
     with Image.open(path) as im:
         a = np.array(im.convert("RGB").resize((int(width), int(height)), Image.BICUBIC))  # a writable copy
     t = torch.from_numpy(a).permute(2, 0, 1).contiguous().to(torch.float32).div(255)
-    mean = torch.as_tensor(IMAGENET_MEAN, dtype=torch.float32).view(3, 1, 1)
-    std = torch.as_tensor(IMAGENET_STD, dtype=torch.float32).view(3, 1, 1)
+    mean = torch.as_tensor(mean, dtype=torch.float32).view(3, 1, 1)
+    std = torch.as_tensor(std, dtype=torch.float32).view(3, 1, 1)
     return t.sub_(mean).div_(std)
 
 
@@ -92,7 +93,8 @@ def plan(args) -> dict:
     if args.height < spec.patch or args.width < spec.patch or args.stride_size < 1:
         raise _lib.DvtError(f"--height {args.height} --width {args.width} --stride_size {args.stride_size}: the frame must hold "
                             f"one {spec.patch}-pixel patch and the stride must be positive")
-    cfg = _vit.vit_config(spec.dim, spec.depth, spec.patch, args.stride_size, args.height, args.width, spec.n_reg)
+    cfg = _vit.vit_config(spec.dim, spec.depth, spec.patch, args.stride_size, args.height, args.width, spec.n_reg,
+                          pos_has_cls=spec.pos_has_cls)
     stats = VD.load_stats(args.stats, args.stats_prefix)
     VD.check_geometry((cfg.grid_h, cfg.grid_w), cfg.dim, args.num_clusters, stats)
     scenes = [(scene_name(d), scene_frames(d)) for d in args.frames]
@@ -129,7 +131,7 @@ def main(args, device=None) -> dict:
     vit = PretrainedViTWrapper(args.model, stride=args.stride_size, checkpoint_path=args.vit_checkpoint,
                                img_size=(args.height, args.width), allow_random_init=args.allow_random_vit, dtype=args.dtype)
     eng = VD.VideoDemoEngine(device, todo["grid_hw"], todo["channels"], (args.height, args.width), todo["stats"],
-                             args.num_clusters, args.seed, IMAGENET_MEAN, IMAGENET_STD)
+                             args.num_clusters, args.seed, *model_statistics(args.model))
     try:
         import imageio  # noqa: F401
     except ImportError:
@@ -165,7 +167,7 @@ def main(args, device=None) -> dict:
             for i, path in enumerate(frames):
                 if errors:
                     break
-                img = load_frame(path, args.height, args.width).pin_memory().to(device, non_blocking=True)
+                img = load_frame(path, args.height, args.width, *model_statistics(args.model)).pin_memory().to(device, non_blocking=True)
                 feats = vit.features_nhwc(img[None])
                 if i == 0:
                     eng.fit(feats)

@@ -76,9 +76,15 @@ _lib.register_signatures({
     "dvt_vit_forward_cls": (_I, [C.POINTER(VitConfig), C.POINTER(VitWeights), _P, _P, _P, _I, _I, _P, _P]),
     "dvt_vit_forward_f32_cls": (_I, [C.POINTER(VitConfig), C.POINTER(VitWeights), _P, _P, _P, _I, _I, _P, _P]),
     "dvt_vit_forward_f32x3_cls": (_I, [C.POINTER(VitConfig), C.POINTER(VitWeights), _P, _P, _P, _I, _I, _P, _P]),
+    "dvt_vit_im2col": (_I, [C.POINTER(VitConfig), _P, _P, _I, _P]),
+    "dvt_vit_im2col_f32": (_I, [C.POINTER(VitConfig), _P, _P, _I, _P]),
     "dvt_vit_ln_cast_stats": (_I, [_P, _P, _P, _I, _I, C.c_float, _P]),
     "dvt_vit_gemm_residual_stats": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_float, _P]),
 })
+
+
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+HALF_MEAN, HALF_STD = (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)
 
 
 @dataclass(frozen=True)
@@ -90,6 +96,21 @@ class VitSpec:
     ls_init: float = 1e-5  # DINOv2 LayerScale init
     n_reg: int = 0         # register tokens (the *_reg4_* checkpoints; timm: no_embed_class=True)
     mlp: str = "gelu"      # "gelu": fc2(GELU(fc1 x)), hidden 4 dim; "swiglu": timm SwiGLUPacked (ViT-g/14), hidden 4096
+    # pos_embed carries a cls row.  None: it follows from the registers, as for DINOv2 (reg4: no_embed_class=True).  DeiT-III has
+    # no registers and no cls row either (timm deit3_*: no_embed_class=True)
+    pos_cls: bool | None = None
+    layer_scale: bool = True  # the checkpoint has blocks.N.ls{1,2}.gamma (DINOv2, DeiT-III); DINO and AugReg have none
+    mean: tuple = IMAGENET_MEAN  # timm data config of the checkpoint (AugReg: 0.5 / 0.5)
+    std: tuple = IMAGENET_STD
+
+    @property
+    def pos_has_cls(self) -> int:
+        return int(self.n_reg == 0 if self.pos_cls is None else self.pos_cls)
+
+    @property
+    def n_pos(self) -> int:
+        """Rows of the checkpoint's position table."""
+        return self.pos_has_cls + (self.img_size // self.patch) ** 2
 
 
 # the DINOv2 ViT-S/B/L/g backbones of the reference's MODEL_LIST with and without register tokens
@@ -103,7 +124,44 @@ SPECS = {
     "vit_large_patch14_reg4_dinov2.lvd142m": VitSpec(1024, 24, n_reg=4),
     "vit_giant_patch14_dinov2.lvd142m": VitSpec(1536, 40, mlp="swiglu"),
     "vit_giant_patch14_reg4_dinov2.lvd142m": VitSpec(1536, 40, n_reg=4, mlp="swiglu"),
+    # the other families whose block is the block above (LayerNorm eps 1e-6, biased qkv, exact GELU, head_dim 64), restated
+    # from the published architectures (timm is absent: parity unpinned).  DINO and AugReg: cls + patches position table, no
+    # LayerScale; DeiT-III: LayerScale, position table on the patches only; AugReg normalises with 0.5 / 0.5
+    "vit_small_patch16_224.dino": VitSpec(384, 12, patch=16, img_size=224, layer_scale=False),
+    "vit_small_patch8_224.dino": VitSpec(384, 12, patch=8, img_size=224, layer_scale=False),
+    "vit_base_patch16_224.dino": VitSpec(768, 12, patch=16, img_size=224, layer_scale=False),
+    "vit_base_patch8_224.dino": VitSpec(768, 12, patch=8, img_size=224, layer_scale=False),
+    "deit3_base_patch16_224.fb_in1k": VitSpec(768, 12, patch=16, img_size=224, pos_cls=False),
+    "vit_base_patch16_384.augreg_in21k_ft_in1k": VitSpec(768, 12, patch=16, img_size=384, layer_scale=False,
+                                                         mean=HALF_MEAN, std=HALF_STD),
 }
+
+# ids of the reference's MODEL_LIST that are NOT built, and what their block needs that the kernels do not compute
+NOT_BUILT = {
+    "vit_base_patch16_clip_384.laion2b_ft_in12k_in1k": "CLIP: a LayerNorm (norm_pre) after the patch embedding, a patch embedding "
+                                                       "without bias, LayerNorm eps 1e-5",
+    "vit_base_patch16_clip_224.openai": "CLIP: a LayerNorm (norm_pre) after the patch embedding, a patch embedding without bias, "
+                                        "LayerNorm eps 1e-5, and an activation that cannot be pinned without timm",
+    "vit_base_patch16_224.mae": "MAE: out of scope",
+    "vit_large_patch16_224.mae": "MAE: out of scope",
+    "vit_huge_patch14_224.mae": "MAE: out of scope",
+    "eva02_base_patch16_clip_224.merged2b": "EVA-02: rotary position embedding and a sub-LN SwiGLU MLP",
+}
+
+
+def model_statistics(model: str | None) -> tuple:
+    """(mean, std) of the model's data config: ImageNet's, 0.5 / 0.5 for AugReg; ImageNet's for an id outside SPECS."""
+    spec = SPECS.get(model)
+    return (tuple(spec.mean), tuple(spec.std)) if spec is not None else (IMAGENET_MEAN, IMAGENET_STD)
+
+
+def require_dinov2_layout(model: str | None, consumer: str, why: str) -> None:
+    """Refuse, by name and before anything is written, a backbone of SPECS that `consumer` is not built for: the drivers whose
+    kernels or data path assume the DINOv2 layout (patch 14, LayerScale parameters, ImageNet statistics).  `why` names what."""
+    spec = SPECS.get(model)
+    if spec is not None and (spec.patch != 14 or not spec.layer_scale or spec.pos_cls is not None):
+        raise _lib.DvtError(f"{model}: {consumer} is built for the DINOv2 patch-14 backbones only ({why}); the extractor, "
+                            "stage 1, stage 2 and the video demo take this model; nothing was written")
 
 # Consumers of the extractor that hold a feature row in a fixed number of register slots (the per-image fit, the loss rows,
 # VisEngine, the video kernels, the stage-2 / stage-3 kernels): built for feature widths up to this
@@ -171,8 +229,9 @@ def resample_pos_embed(pos_embed: torch.Tensor, new_grid: tuple[int, int], n_pre
 
 
 def vit_config(dim: int, depth: int, patch: int, stride: int, img_h: int, img_w: int,
-               n_reg: int = 0, row_pad: int = 128, mlp: str = "gelu") -> VitConfig:
-    """`row_pad`: an image's tokens are padded to a multiple of it.  128 is what dvt_vit_config writes and what the fp32 /
+               n_reg: int = 0, row_pad: int = 128, mlp: str = "gelu", pos_has_cls: int | None = None) -> VitConfig:
+    """`pos_has_cls`: whether the position table has a cls row; None = what the C side derives from the registers (DINOv2).
+    `row_pad`: an image's tokens are padded to a multiple of it.  128 is what dvt_vit_config writes and what the fp32 /
     bf16x3 forwards need; the bf16 forward takes any multiple of 32 (round 6): 1370 tokens -> 1376 rows instead of 1408,
     2.3 % fewer rows through every GEMM and row-local kernel (DVT_VIT_ROW_PAD overrides, for A/B runs)."""
     cfg = VitConfig()
@@ -188,6 +247,10 @@ def vit_config(dim: int, depth: int, patch: int, stride: int, img_h: int, img_w:
         if row_pad % 32 or row_pad <= 0:
             raise _lib.DvtError(f"row_pad must be a positive multiple of 32, not {row_pad}")
         cfg.s_pad = -(-cfg.n_tokens // row_pad) * row_pad
+    if pos_has_cls is not None:
+        if int(pos_has_cls) not in (0, 1):
+            raise _lib.DvtError(f"pos_has_cls must be 0 or 1, not {pos_has_cls!r}")
+        cfg.pos_has_cls = int(pos_has_cls)
     sizes = (C.c_int64 * 3)()
     _lib.lib().dvt_vit_struct_sizes(sizes)
     if list(sizes) != [C.sizeof(VitConfig), C.sizeof(VitBlockWeights), C.sizeof(VitWeights)]:
@@ -197,11 +260,13 @@ def vit_config(dim: int, depth: int, patch: int, stride: int, img_h: int, img_w:
 
 def random_state_dict(dim: int, depth: int, patch: int, n_tokens: int, seed: int = 0,
                       ls_gamma: float | None = 1e-5, well_conditioned: bool = False,
-                      n_reg: int = 0, mlp: str = "gelu") -> dict:
+                      n_reg: int = 0, mlp: str = "gelu", layer_scale: bool = True) -> dict:
     """Random-init weights in the timm layout (trunc_normal(0.02)-like matrices).  With
     `well_conditioned` biases / LayerScale / norm affine are random O(1) so that parity tests
     exercise every term (LayerScale 1e-5 would hide block errors).  mlp="swiglu": the SwiGLUPacked MLP of ViT-g/14
-    (fc1 [2 H, dim] gates first, fc2 [dim, H], H = swiglu_hidden(dim)); the default output is what it always was."""
+    (fc1 [2 H, dim] gates first, fc2 [dim, H], H = swiglu_hidden(dim)); the default output is what it always was.
+    `n_tokens` is the row count of pos_embed (with or without a cls row: the caller's choice); layer_scale=False leaves out
+    the ls1 / ls2 keys (DINO, AugReg)."""
     if mlp not in ("gelu", "swiglu"):
         raise _lib.DvtError(f"mlp must be 'gelu' or 'swiglu', not {mlp!r}")
     hid = swiglu_hidden(dim) if mlp == "swiglu" else 4 * dim
@@ -232,7 +297,7 @@ def random_state_dict(dim: int, depth: int, patch: int, n_tokens: int, seed: int
         sd[p + "mlp.fc1.bias"] = rn(fc1_n, std=0.2) if well_conditioned else torch.zeros(fc1_n)
         sd[p + "mlp.fc2.weight"] = rn(dim, hid, std=ws * 0.5)
         sd[p + "mlp.fc2.bias"] = rn(dim, std=0.2) if well_conditioned else torch.zeros(dim)
-        for nm in ("ls1", "ls2"):
+        for nm in (("ls1", "ls2") if layer_scale else ()):
             sd[p + nm + ".gamma"] = (0.5 + torch.rand(dim, generator=g) if well_conditioned
                                      else torch.full((dim,), float(ls_gamma)))
     return sd
@@ -324,8 +389,11 @@ class HipViT:
     """Device-resident weights + the forward launcher."""
 
     def __init__(self, state_dict: dict, patch: int, stride: int, img_size: tuple[int, int],
-                 device: torch.device | str = "cuda", dtype: str = "bfloat16", matmul: str = "highest"):
-        """dtype "bfloat16": bf16 operands / fp32 accumulate (the reference's `--dtype bfloat16` autocast mode);
+                 device: torch.device | str = "cuda", dtype: str = "bfloat16", matmul: str = "highest",
+                 pos_has_cls: int | None = None):
+        """`pos_has_cls`: whether pos_embed's first row belongs to cls (VitSpec.pos_has_cls); None = read from the table's row
+        count, a square (patches only: the reg4 models, DeiT-III) or a square plus one.
+        dtype "bfloat16": bf16 operands / fp32 accumulate (the reference's `--dtype bfloat16` autocast mode);
         "float32": fp32 operands everywhere (its default, autocast off) -- 16x less matrix throughput.
         `matmul` (float32 only) is torch.set_float32_matmul_precision's vocabulary: "highest" (default, what the reference
         runs with) = exact-fp32 matrix cores; "high" = every matrix product (linear layers, q.k^T, p.v) on the bf16 pipe over
@@ -349,14 +417,20 @@ class HipViT:
         if self.mlp == "swiglu" and self.x3:
             raise _lib.DvtError(f"ViT with a SwiGLU MLP (dim {dim}, depth {depth}: the vit_giant_patch14 models): matmul=\"high\" "
                                 "(bf16x3) is built for the GELU MLP only; use matmul=\"highest\" or dtype=\"bfloat16\"")
+        n_reg = int(sd["reg_token"].shape[1]) if "reg_token" in sd else 0
+        n_pos = int(sd["pos_embed"].shape[1])
+        if pos_has_cls is None:
+            pos_has_cls = 0 if math.isqrt(n_pos) ** 2 == n_pos else 1
+        if n_reg and pos_has_cls:
+            raise _lib.DvtError("a ViT with register tokens carries no cls row in pos_embed (timm: no_embed_class=True)")
         if self.device.type != "cuda":
             raise _lib.DvtError("HipViT needs a HIP device; there is no CPU fallback")
-        n_reg = int(sd["reg_token"].shape[1]) if "reg_token" in sd else 0
         row_pad = 128  # (the bf16x3 forward: its split kernels walk 64-token blocks of whole 128-row images)
         if not self.x3:  # bf16 (round 6) and exact fp32 (round 6, second session): any multiple of 32 -- 1370 tokens -> 1376 rows
             env = os.environ.get("DVT_VIT_ROW_PAD", "")
             row_pad = int(env) if env.isdigit() and int(env) > 0 else 32
-        self.cfg = vit_config(dim, depth, patch, stride, img_size[0], img_size[1], n_reg, row_pad=row_pad, mlp=self.mlp)
+        self.cfg = vit_config(dim, depth, patch, stride, img_size[0], img_size[1], n_reg, row_pad=row_pad, mlp=self.mlp,
+                              pos_has_cls=pos_has_cls)
         cfg = self.cfg
         if self.mlp == "swiglu" and fc2_k != cfg.mlp_dim:
             raise _lib.DvtError(f"SwiGLU hidden width {fc2_k} is not the {cfg.mlp_dim} of dim {dim}")

@@ -197,6 +197,12 @@ int dvt_vit_gemm_residual_stats(const void* a, const void* w, const float* b, co
 /* xb (bf16 [rows, dim]) = bf16(x fp32 [rows, dim]) and stats[rows] (float2) = (mean, rstd) in two passes: what the folded
  * forward runs behind the patch embedding.  dim % 4 == 0, dim <= 1536. */
 int dvt_vit_ln_cast_stats(const float* x, void* xb, void* stats, int rows, int dim, float eps, void* stream);
+/* The im2col of the patch embedding alone, as dvt_vit_forward / dvt_vit_forward_f32 launch it: col [batch * s_pad, k_patch]
+ * (bf16 / fp32), row b * s_pad + s = the patch of token s (channel, ky, kx order, zero behind 3 patch^2), prefix and pad rows
+ * zero.  Patch sizes 14, 16 and 8 with an even stride and image width move pairs (compile-time divisors); every other
+ * geometry takes the generic kernel.  DVT_E_BADARG where the grid does not fit the image. */
+int dvt_vit_im2col(const DvtVitConfig* h_cfg, const float* img, void* col, int batch, void* stream);
+int dvt_vit_im2col_f32(const DvtVitConfig* h_cfg, const float* img, float* col, int batch, void* stream);
 /* The qkv GEMM of dvt_vit_forward: x bf16 [m, dim] . w^T (bf16 [3 dim, dim]) + b, q columns times q_scale (0: as they are),
  * q | k into qk bf16 [m, 2 dim], v TRANSPOSED per head into vt bf16 [batch, heads, 64, s_pad] (the layout dvt_vit_attention
  * reads).  m = batch * s_pad rounded up to 256 (s_pad % 32 == 0): the phantom rows behind batch * s_pad get their q | k
