@@ -19,9 +19,9 @@
 //   depth_pgrad_partial_kernel  G_s = dZ_s^T X_s and the column sums of dZ_s over slabs of 256 rows of one image
 //   depth_pgrad_finish_kernel   dW[:, :C] = sum_s G_s, dW[:, C:] = sum_b (sum of dZ_b) (x) cls_b, db
 //
-// Source index of a bilinear resize (PyTorch upsample_bilinear2d, align_corners=False):
-//   src = (in / out) (dst + 0.5) - 0.5, clamped below at 0;  i0 = (int) src;  i1 = i0 + (i0 < in - 1);  l1 = src - i0.
-#include "dvt_common.h"
+// The bilinear source index and the two 64 x 64 tiles (logits, parameter-gradient slab) are dvt_head_dev.h's, shared with
+// the segmentation head.
+#include "dvt_head_dev.h"
 #include "../../include/dvt_depth.h"
 
 #include <assert.h>
@@ -34,22 +34,6 @@ constexpr int kLossPix = 1024;  // pixels per loss record
 constexpr int kClipBlock = 4096;
 constexpr float kEps = 1e-3f;   // SigLoss / GradientLoss eps
 constexpr int kMaxCand = (2 * DVT_DEPTH_MAX_UP + 4) * (2 * DVT_DEPTH_MAX_UP + 4);  // cand_range: at most 2 up + 4 per axis
-
-struct Src {
-  int i0, i1;
-  float l0, l1;
-};
-
-__device__ __forceinline__ Src src_index(int dst, int in, float scale) {
-  float s = scale * ((float)dst + 0.5f) - 0.5f;
-  s = s < 0.f ? 0.f : s;
-  Src r;
-  r.i0 = (int)s;
-  r.i1 = r.i0 + (r.i0 < in - 1 ? 1 : 0);
-  r.l1 = s - (float)r.i0;
-  r.l0 = 1.f - r.l1;
-  return r;
-}
 
 // Destination indices that can read source index `src` (a superset; the caller tests each with src_index).
 __device__ __forceinline__ void cand_range(int src, float scale, int out, int* lo, int* hi) {
@@ -70,14 +54,6 @@ __device__ __forceinline__ float bilinear(const float* __restrict__ img, int w, 
   const float* r0 = img + (size_t)sy.i0 * w;
   const float* r1 = img + (size_t)sy.i1 * w;
   return sy.l0 * (sx.l0 * r0[sx.i0] + sx.l1 * r0[sx.i1]) + sy.l1 * (sx.l0 * r1[sx.i0] + sx.l1 * r1[sx.i1]);
-}
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // Fixed-order tree sum over the 256 threads of a block; every thread gets the result.
@@ -111,35 +87,12 @@ __global__ __launch_bounds__(256) void depth_cls_kernel(const float* __restrict_
 __global__ __launch_bounds__(256) void depth_logits_kernel(const float* __restrict__ x, int64_t n, int hw, int C, int K,
                                                            const float* __restrict__ params, const float* __restrict__ zc,
                                                            float* __restrict__ z) {
-  __shared__ float xs[32][65];
-  __shared__ float as[32][65];
   const int64_t n0 = (int64_t)blockIdx.x * 64;
   const int k0 = blockIdx.y * 64;
   const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
   float acc[4][4] = {};
-  for (int c0 = 0; c0 < C; c0 += 32) {
-    for (int e = threadIdx.x; e < 64 * 32; e += 256) {
-      const int r = e >> 5, cc = e & 31;
-      const int64_t row = n0 + r;
-      xs[cc][r] = row < n ? x[row * C + c0 + cc] : 0.f;
-      const int kk = k0 + r;
-      as[cc][r] = kk < K ? params[(size_t)kk * 2 * C + c0 + cc] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int cc = 0; cc < 32; ++cc) {
-      float a[4], b[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = xs[cc][ty * 4 + i];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) b[j] = as[cc][tx * 4 + j];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
-    }
-    __syncthreads();
-  }
+  head_logits_tile(n0, n, k0, K, C, [&](int64_t row, int c) { return x[row * C + c]; },
+                   [&](int kk, int c) { return params[(size_t)kk * 2 * C + c]; }, acc);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int64_t row = n0 + ty * 4 + i;
@@ -517,48 +470,11 @@ __global__ __launch_bounds__(256) void depth_dz_kernel(const float* __restrict__
 __global__ __launch_bounds__(256) void depth_pgrad_partial_kernel(const float* __restrict__ x, const float* __restrict__ dz,
                                                                   int hw, int Sb, int C, int K, float* __restrict__ Gp,
                                                                   float* __restrict__ dbp) {
-  __shared__ float ds[32][65];
-  __shared__ float xs[32][65];
-  const int c0 = blockIdx.x * 64, k0 = blockIdx.y * 64, slab = blockIdx.z;
+  const int slab = blockIdx.z;
   const int b = slab / Sb, s = slab - b * Sb;
   const int64_t base = (int64_t)b * hw;
   const int64_t r0 = base + (int64_t)s * kSlab, r1 = min(base + hw, r0 + kSlab);
-  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-  float acc[4][4] = {};
-  float dbacc = 0.f;
-  for (int64_t rb = r0; rb < r1; rb += 32) {
-    for (int e = threadIdx.x; e < 32 * 64; e += 256) {
-      const int r = e >> 6, cc = e & 63;
-      const int64_t row = rb + r;
-      const int kk = k0 + cc;
-      ds[r][cc] = (row < r1 && kk < K) ? dz[row * K + kk] : 0.f;
-      xs[r][cc] = row < r1 ? x[row * C + c0 + cc] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int r = 0; r < 32; ++r) {
-      float a[4], bb[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = ds[r][ty * 4 + i];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bb[j] = xs[r][tx * 4 + j];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], bb[j], acc[i][j]);
-    }
-    if (blockIdx.x == 0 && threadIdx.x < 64)
-      for (int r = 0; r < 32; ++r) dbacc += ds[r][threadIdx.x];
-    __syncthreads();
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int kk = k0 + ty * 4 + i;
-    if (kk >= K) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) Gp[((size_t)slab * K + kk) * C + c0 + tx * 4 + j] = acc[i][j];
-  }
-  if (blockIdx.x == 0 && threadIdx.x < 64 && k0 + (int)threadIdx.x < K) dbp[(size_t)slab * K + k0 + threadIdx.x] = dbacc;
+  head_pgrad_slab(r0, r1, slab, dz, C, K, [&](int64_t row, int c) { return x[row * C + c]; }, Gp, dbp);
 }
 
 // Grid (2 C / 64, K).

@@ -335,6 +335,105 @@ int launch_rows(K kernel, int R, hipStream_t s, A... args) {
   return 0;
 }
 
+// ==========================================================================================================
+// Loss and its gradient over rows n_prefix <= t < T of every image, one wave per row (main_denoiser.py:213-217;
+// main_distillation.py: mse + 1 - cosine_similarity(dim=-1).mean()):
+//   o = a + b with ADD (stage 2: the last residual add, n_prefix = 0), o = a without (stage 3: the final-normed x)
+//   l2 = mean((o - t)^2) over the N C loss elements, N = batch * (T - n_prefix) rows
+//   cos_t = o.t / (max(|o|, 1e-8) max(|t|, 1e-8)) (F.cosine_similarity, eps 1e-8);  loss = l2 + 1 - mean_t cos_t
+//   dout = 2 (o - t) / (N C) - (t / (|o| |t|) - cos o / |o|^2) / N
+// acc[0] += sum (o - t)^2, acc[1] += sum cos (block partials, fp32 atomics).  Prefix and padded rows: dout = 0.
+// target and out (may be NULL; receives o) are packed [batch, T - n_prefix, C].
+// ==========================================================================================================
+template <int C, bool ADD>
+__global__ __launch_bounds__(256) void s2_loss_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                      const float* __restrict__ target, float* __restrict__ out,
+                                                      float* __restrict__ dout, float* __restrict__ acc, int n_prefix,
+                                                      int T, int Tp, int R, float inv_el, float inv_tok) {
+  __shared__ float part[2][4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = blockIdx.x * 4 + wave;
+  float se = 0.f, cs = 0.f;
+  if (r < R) {
+    const int img = r / Tp, t = r - img * Tp;
+    Row<C> o;
+    if (t < n_prefix || t >= T) {
+      o.zero();
+      o.store(dout + (size_t)r * C, lane);
+    } else {
+      const size_t pr = (size_t)img * (T - n_prefix) + (t - n_prefix);
+      Row<C> y, tg;
+      o.load(a + (size_t)r * C, lane);
+      if (ADD) y.load(b + (size_t)r * C, lane);
+      tg.load(target + pr * C, lane);
+      float s_d = 0.f, s_ot = 0.f, s_oo = 0.f, s_tt = 0.f;
+      ROW_FOR(j, Row<C>::NJ) {
+        if (ADD) o.v[j] = f4_add(o.v[j], y.v[j]);
+        const float4 d = f4_sub(o.v[j], tg.v[j]);
+        s_d += f4_dot(d, d);
+        s_ot += f4_dot(o.v[j], tg.v[j]);
+        s_oo += f4_dot(o.v[j], o.v[j]);
+        s_tt += f4_dot(tg.v[j], tg.v[j]);
+      }
+      if (out) o.store(out + pr * C, lane);
+      s_d = wave_sum(s_d);
+      s_ot = wave_sum(s_ot);
+      s_oo = wave_sum(s_oo);
+      s_tt = wave_sum(s_tt);
+      const float no = fmaxf(sqrtf(s_oo), 1e-8f), nt = fmaxf(sqrtf(s_tt), 1e-8f);
+      const float cosv = s_ot / (no * nt);
+      const float ka = 2.0f * inv_el, kt = inv_tok / (no * nt), ko = inv_tok * cosv / (no * no);
+      ROW_FOR(j, Row<C>::NJ) {
+        const float4 d = f4_sub(o.v[j], tg.v[j]);
+        float4 g;
+        g.x = ka * d.x - (kt * tg.v[j].x - ko * o.v[j].x);
+        g.y = ka * d.y - (kt * tg.v[j].y - ko * o.v[j].y);
+        g.z = ka * d.z - (kt * tg.v[j].z - ko * o.v[j].z);
+        g.w = ka * d.w - (kt * tg.v[j].w - ko * o.v[j].w);
+        o.v[j] = g;
+      }
+      o.store(dout + (size_t)r * C, lane);
+      se = s_d;
+      cs = cosv;
+    }
+  }
+  if (lane == 0) {
+    part[0][wave] = se;
+    part[1][wave] = cs;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    atomic_add_f32(acc + 0, (part[0][0] + part[0][1]) + (part[0][2] + part[0][3]));
+    atomic_add_f32(acc + 1, (part[1][0] + part[1][1]) + (part[1][2] + part[1][3]));
+  }
+}
+
+// loss_out = {l2 + 1 - cos, l2, 1 - cos, 0} from the two accumulated sums
+__global__ void s2_loss_finish_kernel(const float* __restrict__ acc, float* __restrict__ out, float inv_el, float inv_tok) {
+  const float l2 = acc[0] * inv_el, cl = 1.0f - acc[1] * inv_tok;
+  out[0] = l2 + cl;
+  out[1] = l2;
+  out[2] = cl;
+  out[3] = 0.f;
+}
+
+// Clears acc, runs the two kernels above: dout and loss_out of `norm_batch` images' worth of loss rows (R rows are here).
+template <bool ADD>
+int loss_rows(int C, const float* a, const float* b, const float* target, float* out, float* dout, float* acc, int n_prefix,
+              int T, int Tp, int R, int norm_batch, float* loss_out, hipStream_t s) {
+  const float N = (float)norm_batch * (float)(T - n_prefix);
+  const float inv_el = 1.0f / (N * C), inv_tok = 1.0f / N;
+  const hipError_t e = hipMemsetAsync(acc, 0, 64 * sizeof(float), s);
+  if (e != hipSuccess) return (int)e;
+  switch (C) {
+    case 384: S2_TRY(launch_rows(s2_loss_kernel<384, ADD>, R, s, a, b, target, out, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok)); break;
+    case 768: S2_TRY(launch_rows(s2_loss_kernel<768, ADD>, R, s, a, b, target, out, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok)); break;
+    default: S2_TRY(launch_rows(s2_loss_kernel<1024, ADD>, R, s, a, b, target, out, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok)); break;
+  }
+  hipLaunchKernelGGL(s2_loss_finish_kernel, dim3(1), dim3(1), 0, s, (const float*)acc, loss_out, inv_el, inv_tok);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
 int ln_bwd(int C, const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
            const float* dres, float* dx, float* dgamma, float* dbeta, int R, hipStream_t s) {
   const dim3 grid(dvt_cdiv(R, 32)), blk(256);

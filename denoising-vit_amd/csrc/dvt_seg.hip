@@ -15,9 +15,9 @@
 //   seg_pgrad_finish_kernel /
 //   seg_pgrad_bn_kernel                   dW = G diag(gamma) + db beta^T, db, dgamma = sum_k W o G, dbeta = W^T db
 //
-// Source index of a bilinear resize (PyTorch upsample_bilinear2d, align_corners=False, size given):
-//   src = (in / out) (dst + 0.5) - 0.5, clamped below at 0;  i0 = (int) src;  i1 = i0 + (i0 < in - 1);  l1 = src - i0.
-#include "dvt_common.h"
+// The bilinear source index and the two 64 x 64 tiles (logits, parameter-gradient slab) are dvt_head_dev.h's, shared with
+// the depth head.
+#include "dvt_head_dev.h"
 #include "../../include/dvt_seg.h"
 
 #include <float.h>
@@ -27,24 +27,6 @@ namespace {
 constexpr int kStatRows = 128;  // rows per statistics record
 constexpr int kSlab = 256;      // rows per parameter-gradient slab
 constexpr int kChunk = 16;      // label pixels per chunk of the loss kernel
-
-struct Src {
-  int i0, i1;
-  float l0, l1;
-};
-
-__device__ __forceinline__ Src src_index(int dst, int in, float scale) {
-  float s = scale * ((float)dst + 0.5f) - 0.5f;
-  s = s < 0.f ? 0.f : s;
-  Src r;
-  r.i0 = (int)s;
-  r.i1 = r.i0 + (r.i0 < in - 1 ? 1 : 0);
-  r.l1 = s - (float)r.i0;
-  r.l0 = 1.f - r.l1;
-  return r;
-}
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // ---------------------------------------------------------------------------------------------------- statistics
 // A record holds the mean as an fp32 pair (hi + lo): one fp32 mean of a channel at 1e3 is off by up to 3e-5, which
@@ -157,8 +139,6 @@ __global__ __launch_bounds__(256) void seg_fold_kernel(const float* __restrict__
 // Z [n, K] = (x - mu) A^T + cvec.  Tile 64 rows x 64 classes, 32 channels per stage; thread (ty, tx) owns 4 x 4.
 __global__ __launch_bounds__(256) void seg_logits_kernel(const float* __restrict__ x, int64_t n, int C, int K,
                                                          const float* __restrict__ folded, float* __restrict__ z) {
-  __shared__ float xs[32][65];
-  __shared__ float as[32][65];
   const float* A = folded;
   const float* cvec = folded + (size_t)K * C;
   const float* mu = cvec + K;
@@ -167,29 +147,8 @@ __global__ __launch_bounds__(256) void seg_logits_kernel(const float* __restrict
   const int k0 = blockIdx.y * 64;
   const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
   float acc[4][4] = {};
-  for (int c0 = 0; c0 < C; c0 += 32) {
-    for (int e = threadIdx.x; e < 64 * 32; e += 256) {
-      const int r = e >> 5, cc = e & 31;
-      const int64_t row = n0 + r;
-      xs[cc][r] = row < n ? (x[row * C + c0 + cc] - mu[c0 + cc]) - mu_lo[c0 + cc] : 0.f;
-      const int kk = k0 + r;
-      as[cc][r] = kk < K ? A[(size_t)kk * C + c0 + cc] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int cc = 0; cc < 32; ++cc) {
-      float a[4], b[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = xs[cc][ty * 4 + i];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) b[j] = as[cc][tx * 4 + j];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
-    }
-    __syncthreads();
-  }
+  head_logits_tile(n0, n, k0, K, C, [&](int64_t row, int c) { return (x[row * C + c] - mu[c]) - mu_lo[c]; },
+                   [&](int kk, int c) { return A[(size_t)kk * C + c]; }, acc);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int64_t row = n0 + ty * 4 + i;
@@ -385,50 +344,13 @@ __global__ __launch_bounds__(256) void seg_dz_kernel(const float* __restrict__ R
 __global__ __launch_bounds__(256) void seg_pgrad_partial_kernel(const float* __restrict__ x, const float* __restrict__ dz,
                                                                 int64_t n, int C, int K, const float* __restrict__ folded,
                                                                 float* __restrict__ Gp, float* __restrict__ dbp) {
-  __shared__ float ds[32][65];
-  __shared__ float xs[32][65];
   const float* mu = folded + (size_t)K * C + K;
   const float* invstd = mu + C;
   const float* mu_lo = mu + 2 * C;
-  const int c0 = blockIdx.x * 64, k0 = blockIdx.y * 64, s = blockIdx.z;
+  const int s = blockIdx.z;
   const int64_t r0 = (int64_t)s * kSlab, r1 = min(n, r0 + kSlab);
-  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-  float acc[4][4] = {};
-  float dbacc = 0.f;
-  for (int64_t rb = r0; rb < r1; rb += 32) {
-    for (int e = threadIdx.x; e < 32 * 64; e += 256) {
-      const int r = e >> 6, cc = e & 63;
-      const int64_t row = rb + r;
-      const int kk = k0 + cc;
-      ds[r][cc] = (row < r1 && kk < K) ? dz[row * K + kk] : 0.f;
-      const int c = c0 + cc;
-      xs[r][cc] = row < r1 ? ((x[row * C + c] - mu[c]) - mu_lo[c]) * invstd[c] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int r = 0; r < 32; ++r) {
-      float a[4], b[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = ds[r][ty * 4 + i];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) b[j] = xs[r][tx * 4 + j];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
-    }
-    if (blockIdx.x == 0 && threadIdx.x < 64)
-      for (int r = 0; r < 32; ++r) dbacc += ds[r][threadIdx.x];
-    __syncthreads();
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int kk = k0 + ty * 4 + i;
-    if (kk >= K) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) Gp[((size_t)s * K + kk) * C + c0 + tx * 4 + j] = acc[i][j];
-  }
-  if (blockIdx.x == 0 && threadIdx.x < 64 && k0 + (int)threadIdx.x < K) dbp[(size_t)s * K + k0 + threadIdx.x] = dbacc;
+  head_pgrad_slab(r0, r1, s, dz, C, K, [&](int64_t row, int c) { return ((x[row * C + c] - mu[c]) - mu_lo[c]) * invstd[c]; },
+                  Gp, dbp);
 }
 
 // Grid (C / 64, K): G [k, c] = sum_s Gp; dW = gamma_c G + beta_c db_k; db.

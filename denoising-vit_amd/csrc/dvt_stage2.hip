@@ -165,84 +165,6 @@ __global__ __launch_bounds__(256) void s2_softmax_bwd_kernel(const float* __rest
   }
 }
 
-
-// ==========================================================================================================
-// Loss and its gradient, one wave per row (main_denoiser.py:213-217):
-//   o = a + b (the last residual add);  l2 = mean((o - t)^2) over batch*T*C;
-//   cos_t = o.t / (max(|o|, 1e-8) max(|t|, 1e-8)) (F.cosine_similarity, eps 1e-8);  loss = l2 + 1 - mean_t cos_t
-//   dout = 2 (o - t) / (batch T C) - (t / (|o| |t|) - cos o / |o|^2) / (batch T)
-// acc[0] += sum (o - t)^2, acc[1] += sum cos (block partials, fp32 atomics).  Padded rows: dout = 0.
-// ==========================================================================================================
-template <int C>
-__global__ __launch_bounds__(256) void s2_loss_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                      const float* __restrict__ target, float* __restrict__ pred,
-                                                      float* __restrict__ dout, float* __restrict__ acc, int T, int Tp,
-                                                      int R, float inv_el, float inv_tok) {
-  __shared__ float part[2][4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = blockIdx.x * 4 + wave;
-  float se = 0.f, cs = 0.f;
-  if (r < R) {
-    const int img = r / Tp, t = r - img * Tp;
-    Row<C> o;
-    if (t >= T) {
-      o.zero();
-      o.store(dout + (size_t)r * C, lane);
-    } else {
-      Row<C> y, tg;
-      o.load(a + (size_t)r * C, lane);
-      y.load(b + (size_t)r * C, lane);
-      tg.load(target + ((size_t)img * T + t) * C, lane);
-      float s_d = 0.f, s_ot = 0.f, s_oo = 0.f, s_tt = 0.f;
-      ROW_FOR(j, Row<C>::NJ) {
-        o.v[j] = f4_add(o.v[j], y.v[j]);
-        const float4 d = f4_sub(o.v[j], tg.v[j]);
-        s_d += f4_dot(d, d);
-        s_ot += f4_dot(o.v[j], tg.v[j]);
-        s_oo += f4_dot(o.v[j], o.v[j]);
-        s_tt += f4_dot(tg.v[j], tg.v[j]);
-      }
-      if (pred) o.store(pred + ((size_t)img * T + t) * C, lane);
-      s_d = wave_sum(s_d);
-      s_ot = wave_sum(s_ot);
-      s_oo = wave_sum(s_oo);
-      s_tt = wave_sum(s_tt);
-      const float no = fmaxf(sqrtf(s_oo), 1e-8f), nt = fmaxf(sqrtf(s_tt), 1e-8f);
-      const float cosv = s_ot / (no * nt);
-      const float ka = 2.0f * inv_el, kt = inv_tok / (no * nt), ko = inv_tok * cosv / (no * no);
-      ROW_FOR(j, Row<C>::NJ) {
-        const float4 d = f4_sub(o.v[j], tg.v[j]);
-        float4 g;
-        g.x = ka * d.x - (kt * tg.v[j].x - ko * o.v[j].x);
-        g.y = ka * d.y - (kt * tg.v[j].y - ko * o.v[j].y);
-        g.z = ka * d.z - (kt * tg.v[j].z - ko * o.v[j].z);
-        g.w = ka * d.w - (kt * tg.v[j].w - ko * o.v[j].w);
-        o.v[j] = g;
-      }
-      o.store(dout + (size_t)r * C, lane);
-      se = s_d;
-      cs = cosv;
-    }
-  }
-  if (lane == 0) {
-    part[0][wave] = se;
-    part[1][wave] = cs;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    atomic_add_f32(acc + 0, (part[0][0] + part[0][1]) + (part[0][2] + part[0][3]));
-    atomic_add_f32(acc + 1, (part[1][0] + part[1][1]) + (part[1][2] + part[1][3]));
-  }
-}
-
-// loss_out = {l2 + 1 - cos, l2, 1 - cos, 0} from the two accumulated sums
-__global__ void s2_loss_finish_kernel(const float* __restrict__ acc, float* __restrict__ out, float inv_el, float inv_tok) {
-  const float l2 = acc[0] * inv_el, cl = 1.0f - acc[1] * inv_tok;
-  out[0] = l2 + cl;
-  out[1] = l2;
-  out[2] = cl;
-  out[3] = 0.f;
-}
-
 // dpos[t, c] += sum over images of dx[img * Tp + t, c]   (pos_embed broadcasts over the batch)
 __global__ __launch_bounds__(256) void s2_pos_grad_kernel(const float4* __restrict__ dx, float4* __restrict__ dpos, int batch,
                                                           int T, int Tp, int C4) {
@@ -447,18 +369,7 @@ int run(const DvtS2Config* c, const float* params, float* grads, const float* x,
   }
 
   // ---- loss ----
-  const float inv_el = 1.0f / ((float)batch * T * C), inv_tok = 1.0f / ((float)batch * T);
-  {
-    const hipError_t e = hipMemsetAsync(w.acc, 0, 64 * sizeof(float), s);
-    if (e != hipSuccess) return (int)e;
-  }
-  switch (C) {
-    case 384: S2_TRY(launch_rows(s2_loss_kernel<384>, R, s, (const float*)last.x1, (const float*)w.tmp, target, pred, w.d0, w.acc, T, Tp, R, inv_el, inv_tok)); break;
-    case 768: S2_TRY(launch_rows(s2_loss_kernel<768>, R, s, (const float*)last.x1, (const float*)w.tmp, target, pred, w.d0, w.acc, T, Tp, R, inv_el, inv_tok)); break;
-    default: S2_TRY(launch_rows(s2_loss_kernel<1024>, R, s, (const float*)last.x1, (const float*)w.tmp, target, pred, w.d0, w.acc, T, Tp, R, inv_el, inv_tok)); break;
-  }
-  hipLaunchKernelGGL(s2_loss_finish_kernel, dim3(1), dim3(1), 0, s, (const float*)w.acc, loss_out, inv_el, inv_tok);
-  DVT_CHECK_LAUNCH();
+  S2_TRY(loss_rows<true>(C, last.x1, w.tmp, target, pred, w.d0, w.acc, 0, T, Tp, R, batch, loss_out, s));
 
   // ---- backward: d0 holds the gradient w.r.t. the current block's OUTPUT ----
   for (int b = NB - 1; b >= 0; --b) {

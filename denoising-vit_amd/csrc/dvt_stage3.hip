@@ -190,82 +190,6 @@ __global__ __launch_bounds__(256) void s3_ls_bwd_kernel(const float* __restrict_
   for (int c = threadIdx.x; c < C; c += 256) atomic_add_f32(dls + c, (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]));
 }
 
-// ==========================================================================================================
-// Loss over the patch rows (n_prefix <= t < n_tokens) of the final-normed x, one wave per row (main_distillation.py: mse +
-// 1 - cosine_similarity(dim=-1).mean(), as s2_loss_kernel):  dout = 2 (o - t) / (N C) - (t / (|o| |t|) - cos o / |o|^2) / N
-// with N = norm_batch * patches; acc[0] += sum (o - t)^2, acc[1] += sum cos.  Prefix and padded rows: dout = 0.  The patch
-// rows also go to feat (packed [batch, patches, C]) when it is given.
-// ==========================================================================================================
-template <int C>
-__global__ __launch_bounds__(256) void s3_loss_kernel(const float* __restrict__ xf, const float* __restrict__ target,
-                                                      float* __restrict__ feat, float* __restrict__ dout,
-                                                      float* __restrict__ acc, int n_prefix, int T, int Tp, int R,
-                                                      float inv_el, float inv_tok) {
-  __shared__ float part[2][4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = blockIdx.x * 4 + wave;
-  const int NP = T - n_prefix;
-  float se = 0.f, cs = 0.f;
-  if (r < R) {
-    const int img = r / Tp, t = r - img * Tp;
-    Row<C> o;
-    if (t < n_prefix || t >= T) {
-      o.zero();
-      o.store(dout + (size_t)r * C, lane);
-    } else {
-      const size_t pr = (size_t)img * NP + (t - n_prefix);
-      Row<C> tg;
-      o.load(xf + (size_t)r * C, lane);
-      tg.load(target + pr * C, lane);
-      if (feat) o.store(feat + pr * C, lane);
-      float s_d = 0.f, s_ot = 0.f, s_oo = 0.f, s_tt = 0.f;
-      ROW_FOR(j, Row<C>::NJ) {
-        const float4 d = f4_sub(o.v[j], tg.v[j]);
-        s_d += f4_dot(d, d);
-        s_ot += f4_dot(o.v[j], tg.v[j]);
-        s_oo += f4_dot(o.v[j], o.v[j]);
-        s_tt += f4_dot(tg.v[j], tg.v[j]);
-      }
-      s_d = wave_sum(s_d);
-      s_ot = wave_sum(s_ot);
-      s_oo = wave_sum(s_oo);
-      s_tt = wave_sum(s_tt);
-      const float no = fmaxf(sqrtf(s_oo), 1e-8f), nt = fmaxf(sqrtf(s_tt), 1e-8f);
-      const float cosv = s_ot / (no * nt);
-      const float ka = 2.0f * inv_el, kt = inv_tok / (no * nt), ko = inv_tok * cosv / (no * no);
-      ROW_FOR(j, Row<C>::NJ) {
-        const float4 d = f4_sub(o.v[j], tg.v[j]);
-        float4 g;
-        g.x = ka * d.x - (kt * tg.v[j].x - ko * o.v[j].x);
-        g.y = ka * d.y - (kt * tg.v[j].y - ko * o.v[j].y);
-        g.z = ka * d.z - (kt * tg.v[j].z - ko * o.v[j].z);
-        g.w = ka * d.w - (kt * tg.v[j].w - ko * o.v[j].w);
-        o.v[j] = g;
-      }
-      o.store(dout + (size_t)r * C, lane);
-      se = s_d;
-      cs = cosv;
-    }
-  }
-  if (lane == 0) {
-    part[0][wave] = se;
-    part[1][wave] = cs;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    atomic_add_f32(acc + 0, (part[0][0] + part[0][1]) + (part[0][2] + part[0][3]));
-    atomic_add_f32(acc + 1, (part[1][0] + part[1][1]) + (part[1][2] + part[1][3]));
-  }
-}
-
-// loss_out = {l2 + 1 - cos, l2, 1 - cos, 0} from the two accumulated sums
-__global__ void s3_loss_finish_kernel(const float* __restrict__ acc, float* __restrict__ out, float inv_el, float inv_tok) {
-  if (threadIdx.x != 0) return;
-  const float l2 = acc[0] * inv_el, cl = 1.0f - acc[1] * inv_tok;
-  out[0] = l2 + cl;
-  out[1] = l2;
-  out[2] = cl;
-  out[3] = 0.f;
-}
 
 // ---- host side ------------------------------------------------------------------------------------------
 enum { PATCHW = 0, PATCHB, CLS, REG, POS, BLK0 };
@@ -388,15 +312,6 @@ int ls_bwd(int C, const float* dy, const float* f, const float* ls, float* df, f
   return 0;
 }
 
-int loss(int C, const float* xf, const float* target, float* feat, float* dout, float* acc, int n_prefix, int T, int Tp, int R,
-         float inv_el, float inv_tok, hipStream_t s) {
-  switch (C) {
-    case 384: return launch_rows(s3_loss_kernel<384>, R, s, xf, target, feat, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok);
-    case 768: return launch_rows(s3_loss_kernel<768>, R, s, xf, target, feat, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok);
-    default: return launch_rows(s3_loss_kernel<1024>, R, s, xf, target, feat, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok);
-  }
-}
-
 int fork_to(hipStream_t s, hipStream_t sv) {
   if (sv == s) return 0;
   if (hipEventRecord(g_s2_ev_fork, s) != hipSuccess || hipStreamWaitEvent(sv, g_s2_ev_fork, 0) != hipSuccess) return DVT_E_BADARG;
@@ -465,15 +380,7 @@ int run(const DvtVitConfig* c, const float* params, float* grads, const float* i
   }
 
   // ---- loss over the patch rows ----
-  const float NP = (float)(T - c->n_prefix);
-  const float inv_el = 1.0f / ((float)norm_batch * NP * C), inv_tok = 1.0f / ((float)norm_batch * NP);
-  {
-    const hipError_t e = hipMemsetAsync(w.acc, 0, 64 * sizeof(float), s);
-    if (e != hipSuccess) return (int)e;
-  }
-  S2_TRY(loss(C, w.xf, target, feat, w.d1, w.acc, c->n_prefix, T, Tp, R, inv_el, inv_tok, s));
-  hipLaunchKernelGGL(s3_loss_finish_kernel, dim3(1), dim3(64), 0, s, (const float*)w.acc, loss_out, inv_el, inv_tok);
-  DVT_CHECK_LAUNCH();
+  S2_TRY(loss_rows<false>(C, w.xf, nullptr, target, feat, w.d1, w.acc, c->n_prefix, T, Tp, R, norm_batch, loss_out, s));
   // final norm: d0 = d xl
   S2_TRY(ln_bwd(C, w.d1, w.xl, w.meanf, w.rstdf, params + normw, nullptr, w.d0, grads + normw, grads + normb, R, s));
 

@@ -23,12 +23,6 @@ bool shape_ok(int n, int C) {
   return n >= 1 && n <= DVT_VIS_MAX_ROWS && C >= 64 && C <= DVT_VIS_MAX_C && C % 64 == 0;
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // (uint8) (v * 255) as numpy truncates a float32 in [0, 255]; NaN and negatives 0, above 255: 255
 __device__ __forceinline__ uint8_t to_u8(float v) {
   const float f = __fmul_rn(v, 255.0f);
@@ -54,7 +48,7 @@ __global__ void __launch_bounds__(256) k_apply(const float* __restrict__ x, int 
       const float* c = centers + (int64_t)k * C;
       double s = 0.0;
       for (int j = lane; j < C; j += 64) s += (double)c[j] * (double)c[j];
-      s = wave_sum_d(s);
+      s = wave_sum_f64(s);
       if (lane == 0) s_cnorm[k] = sqrt(s);
     }
   }
@@ -73,7 +67,7 @@ __global__ void __launch_bounds__(256) k_apply(const float* __restrict__ x, int 
       xv[r][j] = (live && j < nc) ? x[(int64_t)(row0 + r) * C + j * 64 + lane] : 0.0f;
       s += (double)xv[r][j] * (double)xv[r][j];
     }
-    xn[r] = sqrt(wave_sum_d(s));
+    xn[r] = sqrt(wave_sum_f64(s));
     if (live && norms != nullptr && lane == 0) norms[row0 + r] = (float)xn[r];
   }
 
@@ -100,7 +94,7 @@ __global__ void __launch_bounds__(256) k_apply(const float* __restrict__ x, int 
       float mine = 0.0f;
 #pragma unroll
       for (int c = 0; c < kColBlock; ++c) {
-        const double v = wave_sum_d(acc[r][c]);
+        const double v = wave_sum_f64(acc[r][c]);
         if (lane == c) mine = (float)v;
       }
       if (lane < kColBlock && c0 + lane < m && row0 + r < n) P[(int64_t)(row0 + r) * m + c0 + lane] = mine;
@@ -130,7 +124,7 @@ __global__ void __launch_bounds__(256) k_apply(const float* __restrict__ x, int 
       const double cn = s_cnorm[k];
 #pragma unroll
       for (int r = 0; r < kRowsPerWave; ++r) {
-        const double dot = wave_sum_d(d[r]);
+        const double dot = wave_sum_f64(d[r]);
         const double den = xn[r] * cn;
         const double sim = den > 0.0 ? dot / den : 0.0;
         if (k == 0 || sim > best_sim[r]) {
@@ -202,7 +196,7 @@ __global__ void __launch_bounds__(1024) k_softmax_norm(const float* __restrict__
   const double dt = (double)temp, tmax = (double)vmax / dt;
   double sum = 0.0;
   for (int i = tid; i < n; i += 1024) sum += exp((double)norms[i] / dt - tmax);
-  sum = wave_sum_d(sum);
+  sum = wave_sum_f64(sum);
   if ((tid & 63) == 0) redd[tid >> 6] = sum;
   __syncthreads();
   double total = 0.0;

@@ -53,14 +53,8 @@ VisLayout vis_layout(int n, int C, int K, int R) {
 }
 
 // ---- block-wide reductions in a fixed order (blockDim.x a multiple of 64, at most 1024) -------------------------------
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __device__ double block_sum_d(double v, double* red /* [16] */) {
-  v = wave_sum_d(v);
+  v = wave_sum_f64(v);
   __syncthreads();  // red may still be read from the previous call
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -321,9 +315,9 @@ __global__ void __launch_bounds__(256) k_rows(const float* __restrict__ x, int n
       a1 += v * (double)basis[k * 3 + 1];
       a2 += v * (double)basis[k * 3 + 2];
     }
-    a0 = wave_sum_d(a0);
-    a1 = wave_sum_d(a1);
-    a2 = wave_sum_d(a2);
+    a0 = wave_sum_f64(a0);
+    a1 = wave_sum_f64(a1);
+    a2 = wave_sum_f64(a2);
     if (lane < 3) {
       float v = (float)(lane == 0 ? a0 : (lane == 1 ? a1 : a2));
       if (rgb_min != nullptr) {
@@ -335,7 +329,7 @@ __global__ void __launch_bounds__(256) k_rows(const float* __restrict__ x, int n
   } else if (mode == 1) {
     double s = 0.0;
     for (int k = lane; k < C; k += 64) s += (double)xr[k] * (double)xr[k];
-    s = wave_sum_d(s);
+    s = wave_sum_f64(s);
     if (lane == 0) out[row] = (float)sqrt(s);
   } else {
     const float* xc = x + (int64_t)center * C;
@@ -346,9 +340,9 @@ __global__ void __launch_bounds__(256) k_rows(const float* __restrict__ x, int n
       s += a * a;
       sc += b * b;
     }
-    d = wave_sum_d(d);
-    s = wave_sum_d(s);
-    sc = wave_sum_d(sc);
+    d = wave_sum_f64(d);
+    s = wave_sum_f64(s);
+    sc = wave_sum_f64(sc);
     if (lane == 0) out[row] = (float)(d / (sqrt(s) * sqrt(sc)));
   }
 }
@@ -626,7 +620,7 @@ __global__ void __launch_bounds__(256) k_km_control(int step, int n, int C, int 
     const float* c = p.centers + ((int64_t)r * K + k) * C;
     double s = 0.0;
     for (int j = lane; j < C; j += 64) s += (double)c[j] * (double)c[j];
-    s = wave_sum_d(s);
+    s = wave_sum_f64(s);
     if (lane == 0) p.cnorm[r * K + k] = sqrt(s);
   }
 }
@@ -649,7 +643,7 @@ __global__ void __launch_bounds__(256) k_km_assign(const float* __restrict__ x, 
       xv[j] = j < nc ? x[(int64_t)row * C + j * 64 + lane] : 0.0f;
       s += (double)xv[j] * (double)xv[j];
     }
-    const double xn = sqrt(wave_sum_d(s));
+    const double xn = sqrt(wave_sum_f64(s));
     int best = 0;
     double best_sim = 0.0;
     for (int k = 0; k < K; ++k) {
@@ -657,7 +651,7 @@ __global__ void __launch_bounds__(256) k_km_assign(const float* __restrict__ x, 
 #pragma unroll
       for (int j = 0; j < DVT_VIS_MAX_C / 64; ++j)
         if (j < nc) d += (double)xv[j] * (double)cen[(int64_t)k * C + j * 64 + lane];
-      d = wave_sum_d(d);
+      d = wave_sum_f64(d);
       const double den = xn * p.cnorm[r * K + k];
       const double sim = den > 0.0 ? d / den : 0.0;
       if (k == 0 || sim > best_sim) {

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .arena import FlatAdamW
 
 _P, _I, _I64, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _lib.register_signatures({
@@ -78,36 +79,34 @@ def state_dict_shapes(C_: int, K: int = 256) -> dict:
     return {"decode_head.conv_depth.weight": (K, 2 * C_, 1, 1), "decode_head.conv_depth.bias": (K,)}
 
 
+def param_layout(C_: int, K: int = 256) -> tuple:
+    out = (C.c_int64 * 3)()
+    _lib.check(_lib.lib().dvt_depth_param_offsets(C_, K, out), "dvt_depth_param_offsets")
+    return int(out[2]), {"conv_depth.weight": (int(out[0]), (K, 2 * C_)), "conv_depth.bias": (int(out[1]), (K,))}
+
+
 # ================================================================================================ the head
-class DepthHeadEngine:
+class DepthHeadEngine(FlatAdamW):
     """The depth BNHead on the device.  Features NHWC fp32 [B, h, w, C], cls fp32 [B, C], ground truth fp32 [B, H, W]
-    (0 = invalid)."""
+    (0 = invalid).  `adamw_step` is one group over both head tensors: no paramwise key of the config matches them."""
+    WEIGHT_DECAY = 0.01  # the config's optimizer.weight_decay
 
     def __init__(self, in_channels: int, device, n_bins: int = 256, min_depth: float = 1e-3, max_depth: float = 10.0,
                  upsample: int = 4, seed: int | None = 0):
         if torch.device(device).type != "cuda":
             raise _lib.DvtError("the depth head needs a HIP device; there is no CPU fallback")
-        self.C, self.K, self.up, self.device = int(in_channels), int(n_bins), int(upsample), torch.device(device)
+        self.C, self.K, self.up = int(in_channels), int(n_bins), int(upsample)
         self.min_depth, self.max_depth = float(min_depth), float(max_depth)
-        out = (C.c_int64 * 3)()
-        _lib.check(_lib.lib().dvt_depth_param_offsets(self.C, self.K, out), "dvt_depth_param_offsets")
-        self.off_b, self.total = int(out[1]), int(out[2])
+        super().__init__(*param_layout(self.C, self.K), device)
+        self.off_b = self.layout["conv_depth.bias"][0]
         z = lambda n: torch.zeros(n, device=self.device, dtype=torch.float32)  # noqa: E731
-        self.params, self.grads, self.exp_avg, self.exp_avg_sq = z(self.total), z(self.total), z(self.total), z(self.total)
         self.bins = torch.linspace(self.min_depth, self.max_depth, self.K, dtype=torch.float32).to(self.device)
-        self.step = 0
         self.out, self.clip_out = z(2), z(2)
         self._clip_work = z(int(_lib.lib().dvt_depth_clip_work_floats(self.total)))
-        self._work = None
         self._eval_work = None
         self.init_parameters(seed)
 
     # ---- parameters -------------------------------------------------------------------------------
-    def views(self, arena: torch.Tensor | None = None) -> dict:
-        arena = self.params if arena is None else arena
-        return {"conv_depth.weight": arena[:self.off_b].view(self.K, 2 * self.C),
-                "conv_depth.bias": arena[self.off_b:self.off_b + self.K]}
-
     def init_parameters(self, seed: int | None = 0) -> None:
         """torch's Conv2d default (the reference's head defines no init of its own): U(-1 / sqrt(fan_in), 1 / sqrt(fan_in))
         for weight and bias, fan_in = 2 C."""
@@ -130,14 +129,6 @@ class DepthHeadEngine:
         v["conv_depth.weight"].copy_(sd["decode_head.conv_depth.weight"].reshape(self.K, 2 * self.C))
         v["conv_depth.bias"].copy_(sd["decode_head.conv_depth.bias"])
 
-    def optimizer_state(self) -> dict:
-        return {"step": self.step, "exp_avg": self.exp_avg.cpu().clone(), "exp_avg_sq": self.exp_avg_sq.cpu().clone()}
-
-    def load_optimizer_state(self, st: dict) -> None:
-        self.step = int(st["step"])
-        self.exp_avg.copy_(st["exp_avg"])
-        self.exp_avg_sq.copy_(st["exp_avg_sq"])
-
     # ---- kernels ----------------------------------------------------------------------------------
     def _check(self, feats: torch.Tensor, cls: torch.Tensor) -> None:
         _lib.require_cuda(feats, cls)
@@ -146,14 +137,11 @@ class DepthHeadEngine:
         if cls.dtype != torch.float32 or not cls.is_contiguous() or tuple(cls.shape) != (feats.shape[0], self.C):
             raise _lib.DvtError(f"cls must be contiguous fp32 [{feats.shape[0]}, {self.C}], got {tuple(cls.shape)} {cls.dtype}")
 
-    def _workspace(self, B: int, h: int, w: int, H: int, W: int) -> torch.Tensor:
+    def _step_workspace(self, B: int, h: int, w: int, H: int, W: int) -> torch.Tensor:
         nb = int(_lib.lib().dvt_depth_workspace_bytes(B, h, w, self.C, self.K, self.up, H, W))
         if nb <= 0:
             raise _lib.DvtError(f"dvt_depth_workspace_bytes: invalid shape (batch {B}, {h} x {w} tokens, labels {H} x {W})")
-        if self._work is None or self._work.numel() < nb:
-            self._work = None
-            self._work = torch.empty(nb, device=self.device, dtype=torch.uint8)
-        return self._work
+        return self._workspace(nb)
 
     def train_step(self, feats: torch.Tensor, cls: torch.Tensor, depth_gt: torch.Tensor, it: int) -> torch.Tensor:
         """One training step of the head at global iteration `it` (SigLoss warms up while it < 100): writes `grads`;
@@ -165,7 +153,7 @@ class DepthHeadEngine:
         if depth_gt.dtype != torch.float32 or depth_gt.dim() != 3 or depth_gt.shape[0] != B or not depth_gt.is_contiguous():
             raise _lib.DvtError(f"depth_gt must be contiguous fp32 [{B}, H, W], got {tuple(depth_gt.shape)} {depth_gt.dtype}")
         H, W = depth_gt.shape[1:]
-        work = self._workspace(B, h, w, H, W)
+        work = self._step_workspace(B, h, w, H, W)
         _lib.check(_lib.lib().dvt_depth_train_step(
             _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.bins), _lib.ptr(feats), _lib.ptr(cls),
             _lib.ptr(depth_gt), B, h, w, self.C, self.K, self.up, H, W, int(it < WARM_ITERS), GRAD_LOSS_WEIGHT,
@@ -179,20 +167,12 @@ class DepthHeadEngine:
                    "dvt_depth_clip_grad_norm")
         return self.clip_out
 
-    def adamw_step(self, lr: float, weight_decay: float = 0.01, betas=(0.9, 0.999), eps: float = 1e-8,
-                   grad_scale: float = 1.0) -> None:
-        """torch.optim.AdamW over both head tensors (one group: no paramwise key of the config matches them); zeroes `grads`."""
-        self.step += 1
-        _lib.check(_lib.lib().dvt_adamw_step(_lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.exp_avg),
-                                             _lib.ptr(self.exp_avg_sq), self.total, lr, betas[0], betas[1], eps,
-                                             weight_decay, self.step, grad_scale, _lib.stream()), "dvt_adamw_step")
-
     def forward(self, feats: torch.Tensor, cls: torch.Tensor) -> torch.Tensor:
         """The head's depth [B, up h, up w] (not clamped)."""
         self._check(feats, cls)
         B, h, w, _ = feats.shape
         depth = torch.empty(B, self.up * h, self.up * w, device=self.device)
-        work = self._workspace(B, h, w, 0, 0)
+        work = self._step_workspace(B, h, w, 0, 0)
         _lib.check(_lib.lib().dvt_depth_forward(_lib.ptr(self.params), _lib.ptr(self.bins), _lib.ptr(feats), _lib.ptr(cls),
                                                 B, h, w, self.C, self.K, self.up, _lib.ptr(depth), _lib.ptr(work),
                                                 work.numel(), _lib.stream()), "dvt_depth_forward")

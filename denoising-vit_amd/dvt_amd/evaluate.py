@@ -32,6 +32,7 @@ import time
 import numpy as np
 import torch
 
+from . import arena
 from . import depth as DP
 from . import depth_data as DD
 from . import seg as S
@@ -406,28 +407,19 @@ def build_backbone(args, device):
     return S.ViTBackbone(vit._state_dict, vit.patch_size, device, dtype=args.dtype, denoiser=den), C
 
 
+SEG_TENSORS = ["conv_seg.weight", "conv_seg.bias", "bn.weight", "bn.bias"]  # mmseg's parameter order
+DEPTH_TENSORS = ["conv_depth.weight", "conv_depth.bias"]
+
+
 def optimizer_state(head: S.SegHeadEngine, opt_cfg: dict, lr: float) -> dict:
     """torch.optim.AdamW's state_dict layout over the head's four tensors (mmseg's parameter order)."""
-    names = ["conv_seg.weight", "conv_seg.bias", "bn.weight", "bn.bias"]
-    m, v = head.views(head.exp_avg), head.views(head.exp_avg_sq)
-    state = {i: {"step": torch.tensor(float(head.step)), "exp_avg": m[n].detach().cpu().clone(),
-                 "exp_avg_sq": v[n].detach().cpu().clone()} for i, n in enumerate(names)} if head.step else {}
-    group = {"lr": lr, "betas": tuple(opt_cfg.get("betas", (0.9, 0.999))), "eps": 1e-8,
-             "weight_decay": opt_cfg.get("weight_decay", 1e-4), "amsgrad": False, "initial_lr": opt_cfg["lr"],
-             "params": list(range(4))}
-    return {"state": state, "param_groups": [group]}
+    group = arena.adamw_group(lr, opt_cfg.get("weight_decay", 1e-4), opt_cfg.get("betas", (0.9, 0.999)),
+                              initial_lr=opt_cfg["lr"])
+    return arena.adamw_state_dict(head, SEG_TENSORS, group, empty_before_first_step=True)
 
 
 def load_optimizer_state(head: S.SegHeadEngine, st: dict) -> None:
-    names = ["conv_seg.weight", "conv_seg.bias", "bn.weight", "bn.bias"]
-    m, v = head.views(head.exp_avg), head.views(head.exp_avg_sq)
-    for i, n in enumerate(names):
-        s = st["state"].get(i, st["state"].get(str(i)))
-        if s is None:
-            continue
-        m[n].copy_(s["exp_avg"].reshape(m[n].shape))
-        v[n].copy_(s["exp_avg_sq"].reshape(v[n].shape))
-        head.step = int(float(s["step"]))
+    arena.load_adamw_state(head, SEG_TENSORS, st)
 
 
 def save_checkpoint(work_dir, head, cfg, it, seed, lr) -> str:
@@ -581,24 +573,13 @@ def main(argv=None) -> dict:
 # ================================================================================================ depth
 def depth_optimizer_state(head, opt_cfg: dict, lr: float, beta1: float) -> dict:
     """torch.optim.AdamW's state_dict layout over conv_depth.weight and conv_depth.bias."""
-    names = ["conv_depth.weight", "conv_depth.bias"]
-    m, v = head.views(head.exp_avg), head.views(head.exp_avg_sq)
-    state = {i: {"step": torch.tensor(float(head.step)), "exp_avg": m[n].detach().cpu().clone(),
-                 "exp_avg_sq": v[n].detach().cpu().clone()} for i, n in enumerate(names)} if head.step else {}
-    group = {"lr": lr, "betas": (beta1, tuple(opt_cfg.get("betas", (0.9, 0.999)))[1]), "eps": 1e-8,
-             "weight_decay": opt_cfg.get("weight_decay", 0.01), "amsgrad": False, "initial_lr": opt_cfg["lr"], "params": [0, 1]}
-    return {"state": state, "param_groups": [group]}
+    group = arena.adamw_group(lr, opt_cfg.get("weight_decay", 0.01), (beta1, opt_cfg.get("betas", (0.9, 0.999))[1]),
+                              initial_lr=opt_cfg["lr"])
+    return arena.adamw_state_dict(head, DEPTH_TENSORS, group, empty_before_first_step=True)
 
 
 def load_depth_optimizer_state(head, st: dict) -> None:
-    m, v = head.views(head.exp_avg), head.views(head.exp_avg_sq)
-    for i, n in enumerate(["conv_depth.weight", "conv_depth.bias"]):
-        s = st["state"].get(i, st["state"].get(str(i)))
-        if s is None:
-            continue
-        m[n].copy_(s["exp_avg"].reshape(m[n].shape))
-        v[n].copy_(s["exp_avg_sq"].reshape(v[n].shape))
-        head.step = int(float(s["step"]))
+    arena.load_adamw_state(head, DEPTH_TENSORS, st)
 
 
 def gather_metric_rows(rows: torch.Tensor, n_total: int, rank: int, world: int) -> torch.Tensor:

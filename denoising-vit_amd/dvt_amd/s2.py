@@ -14,6 +14,7 @@ import math
 import torch
 
 from . import _lib
+from .arena import FlatAdamW
 
 BLOCK_TENSORS = ["norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight",
                  "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias",
@@ -26,13 +27,12 @@ class S2Config(C.Structure):
                                          "enable_pe")] + [("ln_eps", C.c_float)]
 
 
-_P, _I, _F = C.c_void_p, C.c_int, C.c_float
+_P, _I = C.c_void_p, C.c_int
 _lib.register_signatures({
     "dvt_s2_param_offsets": (_I, [C.POINTER(S2Config), C.POINTER(C.c_int64)]),
     "dvt_s2_workspace_bytes": (C.c_int64, [C.POINTER(S2Config), _I, _I]),
     "dvt_s2_forward": (_I, [C.POINTER(S2Config), _P, _P, _P, _I, _P, C.c_int64, _P]),
     "dvt_s2_train_step": (_I, [C.POINTER(S2Config), _P, _P, _P, _P, _P, _I, _P, C.c_int64, _P, _P]),
-    "dvt_adamw_step": (_I, [_P, _P, _P, _P, C.c_int64, _F, _F, _F, _F, _F, _I, _F, _P]),
 })
 
 
@@ -69,30 +69,19 @@ def param_layout(cfg: S2Config):
     return int(out[1 + 12 * cfg.n_blocks]), names
 
 
-class Stage2Engine:
+class Stage2Engine(FlatAdamW):
     def __init__(self, cfg: S2Config, device: torch.device, inference_only: bool = False):
         """inference_only: a parameter arena and nothing else (no gradient / moment arenas: 3/4 of the memory) --
         what `Denoiser._engine_for` needs for its resized copies."""
         if torch.device(device).type != "cuda":
             raise _lib.DvtError("the stage-2 engine needs a HIP device; there is no CPU fallback")
-        self.cfg, self.device = cfg, torch.device(device)
-        self.total, self.layout = param_layout(cfg)
-        z = lambda: torch.zeros(self.total, device=self.device, dtype=torch.float32)  # noqa: E731
-        self.params = z()
-        self.inference_only = inference_only
-        self.grads = self.exp_avg = self.exp_avg_sq = None
-        if not inference_only:
-            self.grads, self.exp_avg, self.exp_avg_sq = z(), z(), z()
+        self.cfg = cfg
+        super().__init__(*param_layout(cfg), device, inference_only)
         self.loss = torch.zeros(4, device=self.device, dtype=torch.float32)
-        self.step = 0
         self.param_version = 0  # bumped by everything that writes the parameter arena through this engine
-        self._work = {}
+        self._work = {}  # (batch, training) -> buffer: one per mode, sized exactly (not the base's single grow-only one)
 
     # ---- parameters -------------------------------------------------------------------------------
-    def views(self, arena: torch.Tensor | None = None) -> dict:
-        arena = self.params if arena is None else arena
-        return {n: arena[o:o + math.prod(s)].view(s) for n, (o, s) in self.layout.items()}
-
     def init_parameters(self, generator: torch.Generator | None = None) -> None:
         """The reference's initial state: standalone timm `Block`s keep the `nn.Linear` / `nn.LayerNorm`
         defaults (kaiming-uniform(a=sqrt 5) weights and U(+-1/sqrt(fan_in)) biases; ones / zeros), and
@@ -163,12 +152,6 @@ class Stage2Engine:
                                                 w.numel(), _lib.ptr(self.loss), _lib.stream()), "dvt_s2_train_step")
         return self.loss
 
-    def adamw_step(self, lr: float, weight_decay: float, betas=(0.9, 0.999), eps: float = 1e-8,
-                   grad_scale: float = 1.0) -> None:
-        if self.inference_only:
-            raise _lib.DvtError("this engine was built inference_only (no optimizer state)")
-        self.step += 1
+    def adamw_step(self, *args, **kwargs) -> None:
+        super().adamw_step(*args, **kwargs)
         self.param_version += 1
-        _lib.check(_lib.lib().dvt_adamw_step(_lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.exp_avg),
-                                             _lib.ptr(self.exp_avg_sq), self.total, lr, betas[0], betas[1], eps,
-                                             weight_decay, self.step, grad_scale, _lib.stream()), "dvt_adamw_step")

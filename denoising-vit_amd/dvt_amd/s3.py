@@ -10,11 +10,11 @@ gradient is the whole batch's.  `adamw_step` is torch.optim.AdamW over the flat 
 from __future__ import annotations
 
 import ctypes as C
-import math
 
 import torch
 
 from . import _lib
+from .arena import FlatAdamW
 from .vit import VitConfig, vit_config
 
 BLOCK_TENSORS = ["norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias",
@@ -62,27 +62,19 @@ def param_layout(cfg: VitConfig):
     return int(out[n - 1]), layout
 
 
-class Stage3Engine:
+class Stage3Engine(FlatAdamW):
     def __init__(self, cfg: VitConfig, device: torch.device, max_work_bytes: int | None = None):
         """`max_work_bytes`: budget of the activation workspace (default: 80 % of the device memory free after the
         arenas are allocated); `train_step` splits a batch into slices that fit."""
         if torch.device(device).type != "cuda":
             raise _lib.DvtError("the stage-3 engine needs a HIP device; there is no CPU fallback")
-        self.cfg, self.device = cfg, torch.device(device)
-        self.total, self.layout = param_layout(cfg)
-        z = lambda: torch.zeros(self.total, device=self.device, dtype=torch.float32)  # noqa: E731
-        self.params, self.grads, self.exp_avg, self.exp_avg_sq = z(), z(), z(), z()
+        self.cfg = cfg
+        super().__init__(*param_layout(cfg), device)
         self.loss = torch.zeros(4, device=self.device, dtype=torch.float32)
         self._slice_loss = torch.zeros(4, device=self.device, dtype=torch.float32)
-        self.step = 0
         self.max_work_bytes = max_work_bytes
-        self._work = None
 
     # ---- parameters -------------------------------------------------------------------------------
-    def views(self, arena: torch.Tensor | None = None) -> dict:
-        arena = self.params if arena is None else arena
-        return {n: arena[o:o + math.prod(s)].view(s) for n, (o, s) in self.layout.items()}
-
     def load_timm(self, state: dict) -> None:
         """Copy a timm VisionTransformer state dict (DINOv2 layout) into the parameter arena.  Only the checkpoint's own
         position grid is trained: another grid would need the pos_embed resample's backward."""
@@ -123,13 +115,6 @@ class Stage3Engine:
             b = max(1, min(b - 1, budget // need))
         return b
 
-    def _workspace(self, batch: int) -> torch.Tensor:
-        n = self.workspace_bytes(batch)
-        if self._work is None or self._work.numel() < n:
-            self._work = None
-            self._work = torch.empty(n, device=self.device, dtype=torch.uint8)
-        return self._work
-
     def _check(self, img: torch.Tensor, target: torch.Tensor, feat: torch.Tensor | None):
         _lib.require_cuda(img, target, feat)
         c = self.cfg
@@ -149,7 +134,7 @@ class Stage3Engine:
         self._check(img, target, feat)
         B = img.shape[0]
         mb = self.slice_size(B) if micro_batch is None else max(1, min(int(micro_batch), B))
-        w = self._workspace(mb)
+        w = self._workspace(self.workspace_bytes(mb))
         L = _lib.lib()
         if mb >= B:
             _lib.check(L.dvt_s3_train_step(C.byref(self.cfg), _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(img),
@@ -168,11 +153,3 @@ class Stage3Engine:
             cos += 1.0 - self._slice_loss[2]
         self.loss.copy_(torch.stack([l2 + 1.0 - cos, l2, 1.0 - cos, torch.zeros_like(l2)]))
         return self.loss
-
-    def adamw_step(self, lr: float, weight_decay: float, betas=(0.9, 0.999), eps: float = 1e-8,
-                   grad_scale: float = 1.0) -> None:
-        """torch.optim.AdamW over every tensor (one param group, as main_distillation.py builds it); zeroes `grads`."""
-        self.step += 1
-        _lib.check(_lib.lib().dvt_adamw_step(_lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.exp_avg),
-                                             _lib.ptr(self.exp_avg_sq), self.total, lr, betas[0], betas[1], eps,
-                                             weight_decay, self.step, grad_scale, _lib.stream()), "dvt_adamw_step")

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .arena import FlatAdamW
 
 _P, _I, _I64, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _lib.register_signatures({
@@ -99,28 +100,23 @@ def state_dict_shapes(C_: int, K: int) -> dict:
 
 
 # ================================================================================================ the head
-class SegHeadEngine:
-    """BNHead + conv_seg on the device.  Features are NHWC fp32 [B, h, w, C]; labels uint8 [B, H, W] (255 ignored)."""
+class SegHeadEngine(FlatAdamW):
+    """BNHead + conv_seg on the device.  Features are NHWC fp32 [B, h, w, C]; labels uint8 [B, H, W] (255 ignored).
+    `adamw_step` is one group over every head tensor, as mmcv builds it from the config."""
+    WEIGHT_DECAY = 1e-4  # the linear configs' optimizer.weight_decay
 
     def __init__(self, in_channels: int, num_classes: int, device, seed: int | None = 0):
         if torch.device(device).type != "cuda":
             raise _lib.DvtError("the segmentation head needs a HIP device; there is no CPU fallback")
-        self.C, self.K, self.device = int(in_channels), int(num_classes), torch.device(device)
-        self.total, self.layout = param_layout(self.C, self.K)
+        self.C, self.K = int(in_channels), int(num_classes)
+        super().__init__(*param_layout(self.C, self.K), device)
         z = lambda n: torch.zeros(n, device=self.device, dtype=torch.float32)  # noqa: E731
-        self.params, self.grads, self.exp_avg, self.exp_avg_sq = z(self.total), z(self.total), z(self.total), z(self.total)
         self.running = torch.cat([z(self.C), torch.ones(self.C, device=self.device)])
         self.num_batches_tracked = 0
-        self.step = 0
         self.out = z(2)
-        self._work = None
         self.init_parameters(seed)
 
     # ---- parameters -------------------------------------------------------------------------------
-    def views(self, arena: torch.Tensor | None = None) -> dict:
-        arena = self.params if arena is None else arena
-        return {n: arena[o:o + math.prod(s)].view(s) for n, (o, s) in self.layout.items()}
-
     def init_parameters(self, seed: int | None = 0) -> None:
         """mmseg's init: conv_seg ~ N(0, 0.01^2), bias 0; BN weight 1, bias 0."""
         g = torch.Generator().manual_seed(seed) if seed is not None else None
@@ -152,26 +148,12 @@ class SegHeadEngine:
         self.running[self.C:].copy_(sd["decode_head.bn.running_var"])
         self.num_batches_tracked = int(sd["decode_head.bn.num_batches_tracked"])
 
-    def optimizer_state(self) -> dict:
-        return {"step": self.step, "exp_avg": self.exp_avg.cpu().clone(), "exp_avg_sq": self.exp_avg_sq.cpu().clone()}
-
-    def load_optimizer_state(self, st: dict) -> None:
-        self.step = int(st["step"])
-        self.exp_avg.copy_(st["exp_avg"])
-        self.exp_avg_sq.copy_(st["exp_avg_sq"])
-
     # ---- kernels ----------------------------------------------------------------------------------
     def _check_feats(self, feats: torch.Tensor) -> None:
         _lib.require_cuda(feats)
         if feats.dtype != torch.float32 or not feats.is_contiguous() or feats.dim() != 4 or feats.shape[-1] != self.C:
             raise _lib.DvtError(f"features must be contiguous fp32 [B, h, w, {self.C}], got {tuple(feats.shape)} "
                                 f"{feats.dtype}")
-
-    def _workspace(self, nbytes: int) -> torch.Tensor:
-        if self._work is None or self._work.numel() < nbytes:
-            self._work = None
-            self._work = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
-        return self._work
 
     def batch_stats(self, feats: torch.Tensor) -> torch.Tensor:
         """This batch's statistics record [3 C + 4] = (mean_hi, mean_lo, M2, count, 0, 0, 0): what SyncBN gathers across ranks."""
@@ -211,14 +193,6 @@ class SegHeadEngine:
             _lib.ptr(self.out), _lib.stream()), "dvt_seg_train_step")
         self.num_batches_tracked += 1
         return self.out
-
-    def adamw_step(self, lr: float, weight_decay: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
-                   grad_scale: float = 1.0) -> None:
-        """torch.optim.AdamW over every head tensor (one group, as mmcv builds it from the config); zeroes `grads`."""
-        self.step += 1
-        _lib.check(_lib.lib().dvt_adamw_step(_lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.exp_avg),
-                                             _lib.ptr(self.exp_avg_sq), self.total, lr, betas[0], betas[1], eps,
-                                             weight_decay, self.step, grad_scale, _lib.stream()), "dvt_adamw_step")
 
     def forward(self, feats: torch.Tensor) -> torch.Tensor:
         """Inference head (running statistics): logits [B, h, w, K]."""

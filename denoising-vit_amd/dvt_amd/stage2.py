@@ -28,6 +28,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from . import arena
 from . import dist as D
 from .models.online_denoiser import Denoiser
 from .models.vit_wrapper import MODEL_LIST
@@ -167,17 +168,14 @@ class BatchFeeder:
 
 
 # ---- checkpoints -------------------------------------------------------------------------------------------
+def trained_names(model: Denoiser) -> list:
+    return [n for n, _ in model.named_parameters() if not n.startswith("vit.")]
+
+
 def optimizer_state(model: Denoiser, lr: float, weight_decay: float) -> dict:
     """`torch.optim.AdamW.state_dict()` layout over `model.parameters()` order, built from the flat moments."""
-    eng = model.engine
-    m, v = eng.views(eng.exp_avg), eng.views(eng.exp_avg_sq)
-    names = [n for n, _ in model.named_parameters() if not n.startswith("vit.")]
-    state = {i: {"step": torch.tensor(float(eng.step)), "exp_avg": m[n].detach().cpu().clone(),
-                 "exp_avg_sq": v[n].detach().cpu().clone()} for i, n in enumerate(names)}
-    group = {"lr": lr, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": weight_decay, "amsgrad": False,
-             "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-             "params": list(range(len(names)))}
-    return {"state": state, "param_groups": [group]}
+    return arena.adamw_state_dict(model.engine, trained_names(model),
+                                  arena.adamw_group(lr, weight_decay, **arena.TORCH2_GROUP_DEFAULTS))
 
 
 def save_checkpoint(log_dir: str, model: Denoiser, step: int, lr: float, weight_decay: float) -> str:
@@ -185,26 +183,14 @@ def save_checkpoint(log_dir: str, model: Denoiser, step: int, lr: float, weight_
     sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items() if "vit." not in k}
     path = f"{log_dir}/checkpoints/ckpt_{step:06d}.pth"
     torch.save({"denoiser": sd, "optimizer": optimizer_state(model, lr, weight_decay), "step": step}, path)
-    latest = f"{log_dir}/checkpoints/latest.pth"
-    try:
-        os.remove(latest)
-    except FileNotFoundError:
-        pass
-    os.symlink(os.path.abspath(path), latest)
+    arena.link_latest(path, f"{log_dir}/checkpoints/latest.pth")
     return path
 
 
 def load_checkpoint(path: str, model: Denoiser) -> int:
     ck = torch.load(path, map_location="cpu", weights_only=False)
     model.load_state_dict(ck["denoiser"])
-    eng = model.engine
-    names = [n for n, _ in model.named_parameters() if not n.startswith("vit.")]
-    m, v = eng.views(eng.exp_avg), eng.views(eng.exp_avg_sq)
-    for i, n in enumerate(names):
-        st = ck["optimizer"]["state"][i]
-        m[n].copy_(st["exp_avg"].to(eng.device).reshape(m[n].shape))
-        v[n].copy_(st["exp_avg_sq"].to(eng.device).reshape(v[n].shape))
-        eng.step = int(st["step"])
+    arena.load_adamw_state(model.engine, trained_names(model), ck["optimizer"])
     return int(ck["step"]) + 1
 
 

@@ -40,6 +40,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from . import arena
 from . import dist as D
 from .models.vit_wrapper import IMAGENET_MEAN, IMAGENET_STD, MODEL_LIST
 from .stage2 import CosineScheduler, sampler_indices
@@ -174,14 +175,8 @@ def timm_order(names) -> list:
 
 def optimizer_state(eng, lr: float, weight_decay: float) -> dict:
     """`torch.optim.AdamW.state_dict()` of the student's parameters, built from the flat moments."""
-    m, v = eng.views(eng.exp_avg), eng.views(eng.exp_avg_sq)
-    names = timm_order(list(m))
-    state = {i: {"step": torch.tensor(float(eng.step)), "exp_avg": m[n].detach().cpu().clone(),
-                 "exp_avg_sq": v[n].detach().cpu().clone()} for i, n in enumerate(names)}
-    group = {"lr": lr, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": weight_decay, "amsgrad": False,
-             "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-             "params": list(range(len(names)))}
-    return {"state": state, "param_groups": [group]}
+    return arena.adamw_state_dict(eng, timm_order(list(eng.views())),
+                                  arena.adamw_group(lr, weight_decay, **arena.TORCH2_GROUP_DEFAULTS))
 
 
 def model_state(eng) -> dict:
@@ -194,12 +189,7 @@ def save_checkpoint(log_dir: str, eng, step: int, lr: float, weight_decay: float
     """main_distillation.py:264-282: ckpt_{step:06d}.pth + latest.pth symlink."""
     path = f"{log_dir}/checkpoints/ckpt_{step:06d}.pth"
     torch.save({"model": model_state(eng), "optimizer": optimizer_state(eng, lr, weight_decay), "step": step}, path)
-    latest = f"{log_dir}/checkpoints/latest.pth"
-    try:
-        os.remove(latest)
-    except FileNotFoundError:
-        pass
-    os.symlink(os.path.abspath(path), latest)
+    arena.link_latest(path, f"{log_dir}/checkpoints/latest.pth")
     return path
 
 

@@ -154,6 +154,28 @@ def test_step_is_deterministic_and_ignores_workspace_contents(built_lib):
     assert torch.equal(d1, eng.forward(x, cls))
 
 
+def test_step_bits_equal_the_parent(built_lib):
+    """Sharing the logits and parameter-gradient tiles with the segmentation head (csrc/dvt_head_dev.h) did not change a
+    bit: one step and one forward at C 384, B 3, 9 x 11 tokens (one ragged slab per image, the B >= 3 gradient loss; with
+    and without the SigLoss warm-up) and at C 768, B 2, 30 x 39 tokens (five slabs per image, 4 x 256 + 146) give the
+    digests recorded from the parent commit on an MI355X (tests/golden/heads_parent.json; tools/record_head_golden.py
+    wrote it)."""
+    import hashlib
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "heads_parent.json")) as f:
+        want = json.load(f)["depth"]
+
+    def digest(*ts):
+        return hashlib.sha256(b"".join(t.detach().cpu().contiguous().numpy().tobytes() for t in ts)).hexdigest()
+    for C, B, h, w, H, W, it in [(384, 3, 9, 11, 45, 61, 0), (384, 3, 9, 11, 45, 61, 100), (768, 2, 30, 39, 416, 544, 100)]:
+        eng = make_head(C, seed=C + B)
+        x, cls, gt = make_batch(B, h, w, C, H, W, seed=B + it)
+        out = eng.train_step(x, cls, gt, it)
+        got = {"step": digest(out, eng.grads), "forward": digest(eng.forward(x, cls))}
+        assert got == want[f"C{C}_B{B}_{h}x{w}_it{it}"], f"depth head C {C} B {B} {h} x {w} it {it}: bits differ from the parent commit"
+
+
 def test_forward_matches_reference(built_lib):
     eng = make_head(384, seed=2)
     x, cls, _ = make_batch(2, 9, 11, 384, 45, 61, seed=4)

@@ -135,6 +135,28 @@ def test_deterministic_and_nan_workspace(built_lib):
             assert torch.equal(a, b)
 
 
+def test_step_bits_equal_the_parent(built_lib):
+    """Sharing the logits and parameter-gradient tiles with the depth head (csrc/dvt_head_dev.h) did not change a bit: one
+    step and one forward at C 384, K 21 / 150, B 3, 9 x 11 tokens (297 rows: five row tiles with a ragged last one, slabs of
+    256 + 41 rows; one partial class tile / three with a ragged third) give the digests recorded from the parent commit on
+    an MI355X (tests/golden/heads_parent.json; tools/record_head_golden.py wrote it)."""
+    import hashlib
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "heads_parent.json")) as f:
+        want = json.load(f)["seg"]
+
+    def digest(*ts):
+        return hashlib.sha256(b"".join(t.detach().cpu().contiguous().numpy().tobytes() for t in ts)).hexdigest()
+    C = 384
+    for K in (21, 150):
+        eng = make_head(C, K, seed=C + K)
+        x, lab = make_batch(3, 9, 11, C, K, 45, 61, seed=3)
+        out = eng.train_step(x, lab)
+        got = {"step": digest(out, eng.grads, eng.running), "forward": digest(eng.forward(x))}
+        assert got == want[f"C{C}_K{K}"], f"seg head C {C} K {K}: bits differ from the parent commit"
+
+
 def test_adamw_five_steps_with_poly_schedule(built_lib):
     from dvt_amd.seg import poly_lr
     C, K = 384, 21
