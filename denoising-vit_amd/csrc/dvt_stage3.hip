@@ -100,6 +100,94 @@ __global__ __launch_bounds__(256) void s3_embed_bwd_kernel(float4* __restrict__ 
 }
 
 // ==========================================================================================================
+// pos_embed resample (timm resample_abs_pos_embed: F.interpolate(bicubic, antialias, align_corners=False) in fp32 on the
+// square patch part of the table) and its transpose.  The map is linear and separable: per channel O = Wy P Wx^T with the
+// host's tables Wy [gh, g0], Wx [gw, g0] (dvt_amd.s3.pos_tables takes them from torch itself).  All four passes -- x then y
+// forward (ATen's order), y then x backward -- are one contraction along one axis of a [A, B, dim] map:
+//   out[a, b, :] (+)= sum_k w[sel * wo + k * wk] * in[a * ia + b * ib + k * ik, :]      sel = a or b
+// One wave owns 64 float4 columns of one output row: the table entry is the same for every lane (a scalar load), the map's
+// rows are read and written as coalesced 16-byte columns.  k ascends, entries that are exactly zero (everything outside the
+// filter's band) are skipped, one fma per tap: the order is fixed, nothing is atomic, two runs give the same bits.  A null
+// table is the identity along its axis (the resize keeps that axis' length).  The block past the last row carries the cls
+// row over when the table has one.
+// ==========================================================================================================
+struct PosPass {
+  const float* w;      // the table, or nullptr for the identity (K == the selected axis' length)
+  int A, B, K;         // output rows a < A, b < B; taps k < K
+  int sel_b;           // the table row follows b (else a)
+  int wo, wk;          // table index = sel * wo + k * wk
+  int ia, ib, ik;      // input row = a * ia + b * ib + k * ik
+  int dq;              // float4 columns per row (dim / 4)
+};
+
+template <bool ACC>
+__global__ __launch_bounds__(64) void s3_pos_pass_kernel(const float4* __restrict__ in, float4* __restrict__ out,
+                                                         const float4* __restrict__ cls_in, float4* __restrict__ cls_out,
+                                                         PosPass p) {
+  const int q = blockIdx.y * 64 + threadIdx.x;
+  if (q >= p.dq) return;
+  const int r = blockIdx.x;
+  if (r == p.A * p.B) {  // the cls row (launched only when there is one)
+    cls_out[q] = ACC ? f4_add(cls_out[q], cls_in[q]) : cls_in[q];
+    return;
+  }
+  const int a = r / p.B, b = r - a * p.B, sel = p.sel_b ? b : a;
+  const float4* src = in + ((size_t)a * p.ia + (size_t)b * p.ib) * p.dq + q;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (p.w) {
+    const float* w = p.w + (size_t)sel * p.wo;
+    for (int k = 0; k < p.K; ++k) {
+      const float wk = w[(size_t)k * p.wk];
+      if (wk == 0.f) continue;
+      const float4 x = src[(size_t)k * p.ik * p.dq];
+      acc = make_float4(fmaf(wk, x.x, acc.x), fmaf(wk, x.y, acc.y), fmaf(wk, x.z, acc.z), fmaf(wk, x.w, acc.w));
+    }
+  } else {
+    acc = src[(size_t)sel * p.ik * p.dq];
+  }
+  float4* dst = out + (size_t)r * p.dq + q;
+  *dst = ACC ? f4_add(*dst, acc) : acc;
+}
+
+template <bool ACC>
+int pos_pass(const float* in, float* out, const float* cls_in, float* cls_out, const PosPass& p, hipStream_t s) {
+  const dim3 grid(p.A * p.B + (cls_in ? 1 : 0), dvt_cdiv(p.dq, 64));
+  hipLaunchKernelGGL(s3_pos_pass_kernel<ACC>, grid, dim3(64), 0, s, (const float4*)in, (float4*)out, (const float4*)cls_in,
+                     (float4*)cls_out, p);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// wy may be null only when g0 == gh, wx only when g0 == gw
+int pos_check(const float* wy, const float* wx, int g0, int gh, int gw, int dim, int has_cls) {
+  if (g0 < 1 || gh < 1 || gw < 1 || dim < 4 || dim % 4 || (has_cls != 0 && has_cls != 1)) return DVT_E_BADARG;
+  if ((!wy && g0 != gh) || (!wx && g0 != gw)) return DVT_E_BADARG;
+  return 0;
+}
+
+// pos [has_cls + g0 g0, dim] -> out [has_cls + gh gw, dim]; tmp [g0, gw, dim]
+int pos_resample_fwd(const float* pos, float* out, const float* wy, const float* wx, float* tmp, int g0, int gh, int gw,
+                     int dim, int has_cls, hipStream_t s) {
+  const int dq = dim / 4, c = has_cls * dim;
+  // x pass: T[p, j] = sum_q Wx[j, q] P[p, q]
+  S2_TRY(pos_pass<false>(pos + c, tmp, nullptr, nullptr, PosPass{wx, g0, gw, g0, 1, g0, 1, g0, 0, 1, dq}, s));
+  // y pass: O[i, j] = sum_p Wy[i, p] T[p, j]
+  return pos_pass<false>(tmp, out + c, has_cls ? pos : nullptr, out, PosPass{wy, gh, gw, g0, 0, g0, 1, 0, 1, gw, dq}, s);
+}
+
+// dout [has_cls + gh gw, dim] -> dpos [has_cls + g0 g0, dim] += its transpose; tmp [g0, gw, dim]
+int pos_resample_bwd(const float* dout, float* dpos, const float* wy, const float* wx, float* tmp, int g0, int gh, int gw,
+                     int dim, int has_cls, hipStream_t s) {
+  const int dq = dim / 4, c = has_cls * dim;
+  // dT[p, j] = sum_i Wy[i, p] dO[i, j]
+  S2_TRY(pos_pass<false>(dout + c, tmp, nullptr, nullptr, PosPass{wy, g0, gw, gh, 0, 1, g0, 0, 1, gw, dq}, s));
+  // dP[p, q] += sum_j Wx[j, q] dT[p, j]: a gather down the table's column q
+  return pos_pass<true>(tmp, dpos + c, has_cls ? dout : nullptr, dpos, PosPass{wx, g0, g0, gw, 1, 1, g0, gw, 0, 1, dq}, s);
+}
+
+// ==========================================================================================================
 // LayerScale residual add fused with the LayerNorm behind it, one wave per row (timm Block: x = x + ls(f(norm(x))), then the
 // next block's norm1 or the final norm):  sum = a + ls (.) f,  xn = LayerNorm(sum) * gamma + beta, per-row mean / rstd kept.
 // ls == nullptr: sum = a (the first block's norm1).  Rows t >= T: sum = xn = 0, mean = rstd = 0.  LayerNorm arithmetic as
@@ -212,8 +300,8 @@ int check_cfg(const DvtVitConfig* c) {
 
 int64_t n_offsets(const DvtVitConfig* c) { return 8 + (int64_t)DVT_S3_TENSORS_PER_BLOCK * c->depth; }
 
-// out[0 .. n_offsets - 1] as include/dvt_stage3.h lays it out
-void offsets(const DvtVitConfig* c, int64_t* out) {
+// out[0 .. n_offsets - 1] as include/dvt_stage3.h lays it out; g0 > 0: pos_embed keeps the checkpoint's g0 x g0 grid
+void offsets(const DvtVitConfig* c, int64_t* out, int g0 = 0) {
   const int64_t C = c->dim, F = c->mlp_dim, pk = 3LL * c->patch * c->patch;
   int64_t at = 0, i = 0;
   auto put = [&](int64_t floats) {
@@ -224,7 +312,7 @@ void offsets(const DvtVitConfig* c, int64_t* out) {
   put(C);
   put(C);
   put((int64_t)(c->n_prefix - 1) * C);
-  put((int64_t)(c->pos_has_cls + c->grid_h * c->grid_w) * C);
+  put((int64_t)(c->pos_has_cls + (g0 > 0 ? g0 * g0 : c->grid_h * c->grid_w)) * C);
   const int64_t sz[DVT_S3_TENSORS_PER_BLOCK] = {C, C, 3 * C * C, 3 * C, C * C, C, C, C, C, F * C, F, C * F, C, C};
   for (int b = 0; b < c->depth; ++b)
     for (int t = 0; t < DVT_S3_TENSORS_PER_BLOCK; ++t) put(sz[t]);
@@ -241,9 +329,13 @@ struct S3Work {
   float *xl, *xf, *meanf, *rstdf;  // the last block's output and its final norm
   float *col, *wpad, *dwpad, *emb;
   float *d0, *d1, *d2, *dh, *dqkv, *dP, *acc, *wT, *rowdot;
+  float *pos, *dpos, *ptmp;  // the run-grid position table, its gradient and the resample's [g0, gw, dim] intermediate
 };
 
-int64_t carve(const DvtVitConfig* c, int batch, char* base, S3Work* w) {
+// the table's grid differs from the run's: the step resamples pos_embed on its way in and its gradient on the way out
+bool resamples(const DvtVitConfig* c, int g0) { return g0 > 0 && (g0 != c->grid_h || g0 != c->grid_w); }
+
+int64_t carve(const DvtVitConfig* c, int batch, char* base, S3Work* w, int g0 = 0) {
   const int64_t R = (int64_t)batch * c->s_pad, C = c->dim, F = c->mlp_dim;
   const int64_t PP = (int64_t)batch * c->heads * c->s_pad * c->s_pad;
   int64_t o = 0;
@@ -288,6 +380,12 @@ int64_t carve(const DvtVitConfig* c, int batch, char* base, S3Work* w) {
   t.acc = take(64);
   t.wT = take((3 * C > F ? 3 * C : F) * C);
   t.rowdot = take((int64_t)batch * c->heads * c->s_pad);
+  if (resamples(c, g0)) {  // behind everything else: the equal-grid workspace is what it always was
+    const int64_t n = (int64_t)(c->pos_has_cls + c->grid_h * c->grid_w) * C;
+    t.pos = take(n);
+    t.dpos = take(n);
+    t.ptmp = take((int64_t)g0 * c->grid_w * C);
+  }
   if (w) *w = t;
   return o;
 }
@@ -319,13 +417,16 @@ int fork_to(hipStream_t s, hipStream_t sv) {
 }
 
 int run(const DvtVitConfig* c, const float* params, float* grads, const float* img, const float* target, float* feat,
-        int batch, int norm_batch, void* work, int64_t work_bytes, float* loss_out, hipStream_t s) {
+        int batch, int norm_batch, void* work, int64_t work_bytes, float* loss_out, hipStream_t s, int g0 = 0,
+        const float* wy = nullptr, const float* wx = nullptr) {
   S2_TRY(check_cfg(c));
+  const bool rs = resamples(c, g0);
+  if (rs) S2_TRY(pos_check(wy, wx, g0, c->grid_h, c->grid_w, c->dim, c->pos_has_cls));
   if (!params || !grads || !img || !target || !loss_out || !work || batch < 1 || norm_batch < batch) return DVT_E_BADARG;
   S3Work w;
-  if (carve(c, batch, reinterpret_cast<char*>(work), &w) > work_bytes) return DVT_E_BADARG;
+  if (carve(c, batch, reinterpret_cast<char*>(work), &w, g0) > work_bytes) return DVT_E_BADARG;
   int64_t po[8 + DVT_S3_TENSORS_PER_BLOCK * DVT_VIT_MAX_DEPTH];
-  offsets(c, po);
+  offsets(c, po, g0);
   const int C = c->dim, F = c->mlp_dim, T = c->n_tokens, Tp = c->s_pad, H = c->heads, NB = c->depth;
   const int K0 = 3 * c->patch * c->patch, KP = c->k_patch;
   const int R = batch * Tp;
@@ -346,8 +447,9 @@ int run(const DvtVitConfig* c, const float* params, float* grads, const float* i
   hipLaunchKernelGGL(s3_im2col_kernel, dim3(R), dim3(256), 0, s, img, w.col, *c);
   DVT_CHECK_LAUNCH();
   S2_TRY(lin_fwd(w.col, w.wpad, params + po[PATCHB], w.emb, R, C, KP, s));
+  if (rs) S2_TRY(pos_resample_fwd(params + po[POS], w.pos, wy, wx, w.ptmp, g0, c->grid_h, c->grid_w, C, c->pos_has_cls, s));
   hipLaunchKernelGGL(s3_embed_kernel, dim3(R), dim3(256), 0, s, (const float4*)w.emb, (float4*)w.blk[0].xin,
-                     (const float4*)(params + po[CLS]), (const float4*)(params + po[POS]), *c);
+                     (const float4*)(params + po[CLS]), (const float4*)(rs ? w.pos : params + po[POS]), *c);
   DVT_CHECK_LAUNCH();
   S2_TRY(ls_add_ln(C, w.blk[0].xin, nullptr, nullptr, nullptr, P(0, N1W), P(0, N1B), w.blk[0].xn1, w.blk[0].mean1,
                    w.blk[0].rstd1, T, Tp, R, c->ln_eps, s));
@@ -427,10 +529,15 @@ int run(const DvtVitConfig* c, const float* params, float* grads, const float* i
   }
   // ---- token assembly and patch embedding ----
   {
+    if (rs) {  // the assembly's backward adds into a zeroed run-grid gradient; the transpose pass adds that into `grads`
+      const hipError_t e = hipMemsetAsync(w.dpos, 0, sizeof(float) * (size_t)(c->pos_has_cls + c->grid_h * c->grid_w) * C, s);
+      if (e != hipSuccess) return (int)e;
+    }
     const int64_t n = (int64_t)T * (C / 4);
     hipLaunchKernelGGL(s3_embed_bwd_kernel, dim3(dvt_cdiv(n, 256)), dim3(256), 0, s, (float4*)w.d0, (float4*)(grads + po[CLS]),
-                       (float4*)(grads + po[POS]), batch, *c);
+                       (float4*)(rs ? w.dpos : grads + po[POS]), batch, *c);
     DVT_CHECK_LAUNCH();
+    if (rs) S2_TRY(pos_resample_bwd(w.dpos, grads + po[POS], wy, wx, w.ptmp, g0, c->grid_h, c->grid_w, C, c->pos_has_cls, s));
   }
   {
     const hipError_t e = hipMemsetAsync(w.dwpad, 0, sizeof(float) * (size_t)C * KP, s);
@@ -470,4 +577,39 @@ extern "C" int dvt_s3_train_step(const DvtVitConfig* cfg, const float* params, f
                                  const float* target, float* feat_out, int batch, void* work, int64_t work_bytes,
                                  float* loss_out, void* stream) {
   return run(cfg, params, grads, img, target, feat_out, batch, batch, work, work_bytes, loss_out, (hipStream_t)stream);
+}
+
+// ---- another position grid (include/dvt_stage3.h) ---------------------------------------------------------
+extern "C" int dvt_pos_resample_fwd(const float* pos, float* out, const float* wy, const float* wx, float* tmp, int g0,
+                                    int grid_h, int grid_w, int dim, int has_cls, void* stream) {
+  S2_TRY(pos_check(wy, wx, g0, grid_h, grid_w, dim, has_cls));
+  if (!pos || !out || !tmp || !aligned16(pos) || !aligned16(out) || !aligned16(tmp)) return DVT_E_BADARG;
+  return pos_resample_fwd(pos, out, wy, wx, tmp, g0, grid_h, grid_w, dim, has_cls, (hipStream_t)stream);
+}
+
+extern "C" int dvt_pos_resample_bwd(const float* dout, float* dpos, const float* wy, const float* wx, float* tmp, int g0,
+                                    int grid_h, int grid_w, int dim, int has_cls, void* stream) {
+  S2_TRY(pos_check(wy, wx, g0, grid_h, grid_w, dim, has_cls));
+  if (!dout || !dpos || !tmp || !aligned16(dout) || !aligned16(dpos) || !aligned16(tmp)) return DVT_E_BADARG;
+  return pos_resample_bwd(dout, dpos, wy, wx, tmp, g0, grid_h, grid_w, dim, has_cls, (hipStream_t)stream);
+}
+
+extern "C" int dvt_s3_param_offsets_pos(const DvtVitConfig* cfg, int g0, int64_t* out) {
+  if (!out || g0 < 1) return DVT_E_BADARG;
+  S2_TRY(check_cfg(cfg));
+  offsets(cfg, out, g0);
+  return 0;
+}
+
+extern "C" int64_t dvt_s3_workspace_bytes_pos(const DvtVitConfig* cfg, int batch, int g0) {
+  if (check_cfg(cfg) != 0 || batch < 1 || g0 < 1) return -1;
+  return carve(cfg, batch, nullptr, nullptr, g0);
+}
+
+extern "C" int dvt_s3_train_slice_pos(const DvtVitConfig* cfg, int g0, const float* wy, const float* wx, const float* params,
+                                      float* grads, const float* img, const float* target, float* feat_out, int batch,
+                                      int norm_batch, void* work, int64_t work_bytes, float* loss_out, void* stream) {
+  if (g0 < 1) return DVT_E_BADARG;
+  return run(cfg, params, grads, img, target, feat_out, batch, norm_batch, work, work_bytes, loss_out, (hipStream_t)stream, g0,
+             wy, wx);
 }

@@ -6,10 +6,16 @@ activation workspace.  `train_step` is forward + loss + backward of the student 
 get_intermediate_layers(n=1, norm=True) features against the teacher's), gradients accumulated into `grads`; a batch
 larger than the workspace budget runs in slices whose loss terms are normalised by the whole batch, so the accumulated
 gradient is the whole batch's.  `adamw_step` is torch.optim.AdamW over the flat arenas (dvt_adamw_step).
+
+A checkpoint whose position table has another grid than the run (`pos_grid`): `pos_embed` keeps the CHECKPOINT's shape in
+all four arenas; every step resamples it to the run's grid (dvt_pos_resample_fwd, what timm's dynamic_img_size does in every
+forward) and carries the gradient back through the transpose (dvt_pos_resample_bwd, what autograd does there).  The two
+interpolation tables come from torch itself, once per engine (`pos_tables`).
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -27,6 +33,11 @@ _lib.register_signatures({
     "dvt_s3_workspace_bytes": (C.c_int64, [C.POINTER(VitConfig), _I]),
     "dvt_s3_train_step": (_I, [C.POINTER(VitConfig), _P, _P, _P, _P, _P, _I, _P, C.c_int64, _P, _P]),
     "dvt_s3_train_slice": (_I, [C.POINTER(VitConfig), _P, _P, _P, _P, _P, _I, _I, _P, C.c_int64, _P, _P]),
+    "dvt_pos_resample_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "dvt_pos_resample_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "dvt_s3_param_offsets_pos": (_I, [C.POINTER(VitConfig), _I, C.POINTER(C.c_int64)]),
+    "dvt_s3_workspace_bytes_pos": (C.c_int64, [C.POINTER(VitConfig), _I, _I]),
+    "dvt_s3_train_slice_pos": (_I, [C.POINTER(VitConfig), _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, C.c_int64, _P, _P]),
 })
 
 
@@ -36,11 +47,58 @@ def make_config(dim: int, depth: int, patch: int, stride: int, img_h: int, img_w
     return vit_config(dim, depth, patch, stride, img_h, img_w, n_reg, row_pad=128)
 
 
-def tensor_shapes(cfg: VitConfig) -> list:
-    """Shapes of the timm tensors in arena order (names: `param_layout`)."""
+def pos_table(g0: int, g: int) -> torch.Tensor | None:
+    """W [g, g0] (CPU fp32) with `F.interpolate(x, bicubic, antialias, align_corners=False)` along one axis of length g0
+    resized to g == W @ x, read off torch itself by resizing the identity; None when g == g0 (a resize that keeps an axis'
+    length is the identity along it).  Rows have at most 4 non-zero taps when enlarging, more when shrinking (10 at 37 ->
+    16); everything outside that band is exactly zero."""
+    import torch.nn.functional as F
+    if g0 < 1 or g < 1:
+        raise _lib.DvtError(f"a position grid needs at least one row, got {g0} -> {g}")
+    if g == g0:
+        return None
+    return F.interpolate(torch.eye(g0, dtype=torch.float32)[None, None], size=(g, g0), mode="bicubic", antialias=True,
+                         align_corners=False)[0, 0].contiguous()
+
+
+def pos_tables(g0: int, gh: int, gw: int) -> tuple:
+    """(Wy [gh, g0], Wx [gw, g0]) of the resample of a g0 x g0 table to gh x gw: per channel O = Wy P Wx^T."""
+    return pos_table(g0, gh), pos_table(g0, gw)
+
+
+def pos_resample(pos: torch.Tensor, wy, wx, grid: tuple, has_cls: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """dvt_pos_resample_fwd on its own: pos [has_cls + g0 g0, dim] (device fp32) -> [has_cls + gh gw, dim]; wy / wx are
+    device tables (`pos_tables`) or None."""
+    _lib.require_cuda(pos, wy, wx, out)
+    gh, gw = grid
+    dim, g0 = pos.shape[-1], math.isqrt(pos.shape[0] - has_cls)
+    if out is None:
+        out = torch.empty(has_cls + gh * gw, dim, device=pos.device, dtype=torch.float32)
+    tmp = torch.empty(g0 * gw, dim, device=pos.device, dtype=torch.float32)
+    _lib.check(_lib.lib().dvt_pos_resample_fwd(_lib.ptr(pos), _lib.ptr(out), _lib.ptr(wy), _lib.ptr(wx), _lib.ptr(tmp), g0,
+                                               gh, gw, dim, has_cls, _lib.stream()), "dvt_pos_resample_fwd")
+    return out
+
+
+def pos_resample_bwd(dout: torch.Tensor, dpos: torch.Tensor, wy, wx, grid: tuple, has_cls: int) -> torch.Tensor:
+    """dvt_pos_resample_bwd on its own: the transpose of `pos_resample` applied to dout [has_cls + gh gw, dim], ADDED to
+    dpos [has_cls + g0 g0, dim]."""
+    _lib.require_cuda(dout, dpos, wy, wx)
+    gh, gw = grid
+    dim, g0 = dpos.shape[-1], math.isqrt(dpos.shape[0] - has_cls)
+    tmp = torch.empty(g0 * gw, dim, device=dpos.device, dtype=torch.float32)
+    _lib.check(_lib.lib().dvt_pos_resample_bwd(_lib.ptr(dout), _lib.ptr(dpos), _lib.ptr(wy), _lib.ptr(wx), _lib.ptr(tmp), g0,
+                                               gh, gw, dim, has_cls, _lib.stream()), "dvt_pos_resample_bwd")
+    return dpos
+
+
+def tensor_shapes(cfg: VitConfig, pos_grid: int | None = None) -> list:
+    """Shapes of the timm tensors in arena order (names: `param_layout`).  `pos_grid`: the position table keeps a
+    pos_grid x pos_grid patch part (the checkpoint's) instead of the run's grid."""
     d, f, p = cfg.dim, cfg.mlp_dim, cfg.patch
     block = [(d,), (d,), (3 * d, d), (3 * d,), (d, d), (d,), (d,), (d,), (d,), (f, d), (f,), (d, f), (d,), (d,)]
-    return ([(d, 3, p, p), (d,), (1, 1, d), (1, cfg.n_prefix - 1, d), (1, cfg.pos_has_cls + cfg.grid_h * cfg.grid_w, d)]
+    n_pos = cfg.grid_h * cfg.grid_w if pos_grid is None else pos_grid * pos_grid
+    return ([(d, 3, p, p), (d,), (1, 1, d), (1, cfg.n_prefix - 1, d), (1, cfg.pos_has_cls + n_pos, d)]
             + block * cfg.depth + [(d,), (d,)])
 
 
@@ -49,13 +107,16 @@ def param_names(cfg: VitConfig) -> list:
             + [f"blocks.{b}.{t}" for b in range(cfg.depth) for t in BLOCK_TENSORS] + ["norm.weight", "norm.bias"])
 
 
-def param_layout(cfg: VitConfig):
+def param_layout(cfg: VitConfig, pos_grid: int | None = None):
     """-> (total floats, {timm name: (offset, shape)}); `reg_token` only for models with register tokens."""
     n = 8 + 14 * cfg.depth
     out = (C.c_int64 * n)()
-    _lib.check(_lib.lib().dvt_s3_param_offsets(C.byref(cfg), out), "dvt_s3_param_offsets")
+    if pos_grid is None:
+        _lib.check(_lib.lib().dvt_s3_param_offsets(C.byref(cfg), out), "dvt_s3_param_offsets")
+    else:
+        _lib.check(_lib.lib().dvt_s3_param_offsets_pos(C.byref(cfg), int(pos_grid), out), "dvt_s3_param_offsets_pos")
     layout = {}
-    for i, (name, shape) in enumerate(zip(param_names(cfg), tensor_shapes(cfg))):
+    for i, (name, shape) in enumerate(zip(param_names(cfg), tensor_shapes(cfg, pos_grid))):
         if name == "reg_token" and cfg.n_prefix == 1:
             continue
         layout[name] = (int(out[i]), shape)
@@ -63,21 +124,30 @@ def param_layout(cfg: VitConfig):
 
 
 class Stage3Engine(FlatAdamW):
-    def __init__(self, cfg: VitConfig, device: torch.device, max_work_bytes: int | None = None):
-        """`max_work_bytes`: budget of the activation workspace (default: 80 % of the device memory free after the
+    def __init__(self, cfg: VitConfig, device: torch.device, pos_grid: int | None = None,
+                 max_work_bytes: int | None = None):
+        """`pos_grid`: the grid g0 of the checkpoint's position table when `pos_embed` is to keep its [1, cls + g0 g0, dim]
+        shape and be resampled to the run's grid in every step; None: the table is at the run's grid (the layout and the
+        calls without a resample).
+        `max_work_bytes`: budget of the activation workspace (default: 80 % of the device memory free after the
         arenas are allocated); `train_step` splits a batch into slices that fit."""
         if torch.device(device).type != "cuda":
             raise _lib.DvtError("the stage-3 engine needs a HIP device; there is no CPU fallback")
         self.cfg = cfg
-        super().__init__(*param_layout(cfg), device)
+        self.pos_grid = None if pos_grid is None else int(pos_grid)
+        super().__init__(*param_layout(cfg, self.pos_grid), device)
+        self._wy = self._wx = None
+        if self.pos_grid is not None:
+            self._wy, self._wx = (None if t is None else t.to(self.device)
+                                  for t in pos_tables(self.pos_grid, cfg.grid_h, cfg.grid_w))
         self.loss = torch.zeros(4, device=self.device, dtype=torch.float32)
         self._slice_loss = torch.zeros(4, device=self.device, dtype=torch.float32)
         self.max_work_bytes = max_work_bytes
 
     # ---- parameters -------------------------------------------------------------------------------
     def load_timm(self, state: dict) -> None:
-        """Copy a timm VisionTransformer state dict (DINOv2 layout) into the parameter arena.  Only the checkpoint's own
-        position grid is trained: another grid would need the pos_embed resample's backward."""
+        """Copy a timm VisionTransformer state dict (DINOv2 layout) into the parameter arena.  Its position table must be
+        the engine's: the run's grid, or `pos_grid` when the engine was built with one."""
         v = self.views()
         missing = [k for k in v if k not in state]
         if missing:
@@ -85,9 +155,13 @@ class Stage3Engine(FlatAdamW):
         for k, dst in v.items():
             src = state[k]
             if k == "pos_embed" and tuple(src.shape) != tuple(dst.shape):
+                n_old = src.shape[-2] - self.cfg.pos_has_cls
+                g0 = math.isqrt(max(n_old, 0))
+                if src.dim() != 3 or g0 < 1 or g0 * g0 != n_old:
+                    raise _lib.DvtError(f"pos_embed with {n_old} patch positions is not a square grid")
                 raise NotImplementedError(
-                    f"pos_embed {tuple(src.shape)} is not the trained grid {tuple(dst.shape)}: the stage-3 step trains the "
-                    "checkpoint's own position grid only (the pos_embed resample backward is not built)")
+                    f"pos_embed {tuple(src.shape)} is not this engine's table {tuple(dst.shape)}: build the engine with "
+                    f"pos_grid={g0} to train that table and resample it to the run's grid in every step")
             dst.copy_(src.detach().to(self.device, torch.float32).reshape(dst.shape))
 
     def state_dict(self) -> dict:
@@ -96,7 +170,10 @@ class Stage3Engine(FlatAdamW):
 
     # ---- kernels ----------------------------------------------------------------------------------
     def workspace_bytes(self, batch: int) -> int:
-        n = int(_lib.lib().dvt_s3_workspace_bytes(C.byref(self.cfg), batch))
+        if self.pos_grid is None:
+            n = int(_lib.lib().dvt_s3_workspace_bytes(C.byref(self.cfg), batch))
+        else:
+            n = int(_lib.lib().dvt_s3_workspace_bytes_pos(C.byref(self.cfg), batch, self.pos_grid))
         if n <= 0:
             raise _lib.DvtError("dvt_s3_workspace_bytes: invalid configuration")
         return n
@@ -136,19 +213,30 @@ class Stage3Engine(FlatAdamW):
         mb = self.slice_size(B) if micro_batch is None else max(1, min(int(micro_batch), B))
         w = self._workspace(self.workspace_bytes(mb))
         L = _lib.lib()
-        if mb >= B:
+
+        def run_slice(im, tg, ft, n, loss):
+            if self.pos_grid is None:
+                return L.dvt_s3_train_slice(C.byref(self.cfg), _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(im),
+                                            _lib.ptr(tg), _lib.ptr(ft), n, B, _lib.ptr(w), w.numel(), _lib.ptr(loss),
+                                            _lib.stream())
+            return L.dvt_s3_train_slice_pos(C.byref(self.cfg), self.pos_grid, _lib.ptr(self._wy), _lib.ptr(self._wx),
+                                            _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(im), _lib.ptr(tg),
+                                            _lib.ptr(ft), n, B, _lib.ptr(w), w.numel(), _lib.ptr(loss), _lib.stream())
+
+        if mb >= B and self.pos_grid is None:
             _lib.check(L.dvt_s3_train_step(C.byref(self.cfg), _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(img),
                                            _lib.ptr(target), _lib.ptr(feat), B, _lib.ptr(w), w.numel(),
                                            _lib.ptr(self.loss), _lib.stream()), "dvt_s3_train_step")
+            return self.loss
+        if mb >= B:  # norm_batch == batch: the whole step
+            _lib.check(run_slice(img, target, feat, B, self.loss), "dvt_s3_train_slice_pos")
             return self.loss
         l2 = torch.zeros((), device=self.device)
         cos = torch.zeros((), device=self.device)
         for b0 in range(0, B, mb):
             n = min(mb, B - b0)
-            _lib.check(L.dvt_s3_train_slice(C.byref(self.cfg), _lib.ptr(self.params), _lib.ptr(self.grads),
-                                            _lib.ptr(img[b0:]), _lib.ptr(target[b0:]),
-                                            None if feat is None else _lib.ptr(feat[b0:]), n, B, _lib.ptr(w), w.numel(),
-                                            _lib.ptr(self._slice_loss), _lib.stream()), "dvt_s3_train_slice")
+            _lib.check(run_slice(img[b0:], target[b0:], None if feat is None else feat[b0:], n, self._slice_loss),
+                       "dvt_s3_train_slice")
             l2 += self._slice_loss[1]
             cos += 1.0 - self._slice_loss[2]
         self.loss.copy_(torch.stack([l2 + 1.0 - cos, l2, 1.0 - cos, torch.zeros_like(l2)]))

@@ -6,6 +6,11 @@ the stage-2 checkpoint, run under no_grad; loss = MSE + (1 - cosine) over the pa
 param group (weight decay on all of them); sqrt-scaled learning rate with a cosine schedule and 15 % warm-up from 0;
 rank-0 checkpoints `{model, optimizer, step}` with `model.`-prefixed timm keys + a `latest.pth` symlink.
 
+Any `--input_size` / `--stride_size`: when the run's token grid is not the grid of the checkpoint's position table, the
+student keeps `pos_embed` at the CHECKPOINT's shape (parameters, gradients, both AdamW moments, the written checkpoints) and
+every step resamples it to the run's grid and carries the gradient back through the transpose of that map
+(dvt_pos_resample_fwd / _bwd in csrc/dvt_stage3.hip) -- timm's dynamic_img_size forward and its autograd.
+
 MI355X layout: one process per GPU (`python -m torch.distributed.run --nproc-per-node N -m dvt_amd.stage3 ...`).  Every
 rank runs the teacher (csrc/dvt_vit_f32.hip + csrc/dvt_stage2.hip) and the student's forward + loss + backward
 (csrc/dvt_stage3.hip) on its own batch; the student's gradients are ONE flat fp32 arena, summed across ranks by one
@@ -14,8 +19,10 @@ all-reduce per step and scaled by 1/world inside the AdamW kernel (the reference
 Deviations, all forced or harmless:
   * `--input_size` takes two values (what stage3.sh passes) or none (518 x 518).  One value is refused: the reference then
     resizes the short side, and images of different aspect ratios cannot be batched.
-  * only the checkpoint's own position grid is trained (stage3.sh with --auto_stride); another grid would need the backward
-    of timm's pos_embed resample and raises NotImplementedError.
+  * the teacher is built at the grid of the denoiser checkpoint's `pos_embed` (its square row count) and serves the run's
+    grid from a resampled inference copy (`Denoiser._engine_for`): the reference's `Denoiser.forward` resamples its table to
+    the input's grid too, only its `load_state_dict` ties the constructor's grid to the checkpoint.  A checkpoint without
+    `pos_embed` (a denoiser trained with enable_pe=False) runs at any grid, without one.
   * the horizontal flip is drawn from numpy's default_rng((seed, step, position in the global batch)), not from the
     DataLoader workers' torch RNG, which cannot be reproduced outside torch's worker processes.
   * `--grad_checkpointing` recomputes nothing: a batch that does not fit is split into slices (`--micro_batch`) whose
@@ -45,6 +52,7 @@ from . import dist as D
 from .models.vit_wrapper import IMAGENET_MEAN, IMAGENET_STD, MODEL_LIST
 from .stage2 import CosineScheduler, sampler_indices
 from .utils import misc
+from . import _lib
 from .vit import SPECS, model_statistics, require_dinov2_layout
 
 # torchvision.datasets.folder.IMG_EXTENSIONS
@@ -279,6 +287,24 @@ def scheduler(args, lr: float, n_iter: int) -> CosineScheduler:
     return CosineScheduler(lr, args.min_lr, n_iter, warmup_iters=int(n_iter * 0.15), start_warmup_value=0)
 
 
+def square_grid(n_rows: int, what: str) -> int:
+    g = math.isqrt(max(int(n_rows), 0))
+    if g < 1 or g * g != n_rows:
+        raise _lib.DvtError(f"{what} with {n_rows} patch positions is not a square grid")
+    return g
+
+
+def teacher_grid(den_sd: dict, dim: int, gh: int, gw: int) -> tuple:
+    """(noise_map_height, noise_map_width) to build the teacher at: the run's grid when the denoiser checkpoint has no
+    `pos_embed` or has one of exactly gh * gw rows, else the square grid of its rows (`Denoiser._engine_for` then serves the
+    run's grid)."""
+    pe = den_sd.get("pos_embed")
+    if pe is None or pe.numel() // dim == gh * gw:
+        return gh, gw
+    g = square_grid(pe.numel() // dim, "the denoiser checkpoint's pos_embed")
+    return g, g
+
+
 def build_models(args, device):
     """-> (student engine, teacher).  The teacher is `Denoiser(vit=PretrainedViTWrapper(..., dtype="float32"))` with the
     stage-2 checkpoint loaded non-strictly (main_distillation.py:131-141); the student starts from the same ViT weights."""
@@ -288,11 +314,17 @@ def build_models(args, device):
     dim, depth, patch, gh, gw, n_reg = geometry(args)
     vit = PretrainedViTWrapper(args.model, stride=args.stride_size, checkpoint_path=args.vit_checkpoint,
                                img_size=args.input_size, allow_random_init=args.allow_random_vit, dtype="float32")
-    teacher = Denoiser(noise_map_height=gh, noise_map_width=gw, feat_dim=dim, vit=vit, num_blocks=args.num_blocks,
-                       device=device)
-    teacher.load_state_dict(torch.load(args.denoiser_ckpt, map_location="cpu", weights_only=False)["denoiser"],
-                            strict=False)
-    student = Stage3Engine(make_config(dim, depth, patch, args.stride_size, *args.input_size, n_reg), device)
+    den_sd = torch.load(args.denoiser_ckpt, map_location="cpu", weights_only=False)["denoiser"]
+    teacher = Denoiser(*teacher_grid(den_sd, dim, gh, gw), feat_dim=dim, vit=vit, enable_pe="pos_embed" in den_sd,
+                       num_blocks=args.num_blocks, device=device)
+    teacher.load_state_dict(den_sd, strict=False)
+    # the wrapper keeps the checkpoint's table un-resampled: its grid is what the student trains
+    g0 = square_grid(vit._state_dict["pos_embed"].shape[-2] - SPECS[args.model].pos_has_cls, "the ViT checkpoint's pos_embed")
+    pos_grid = None if (g0, g0) == (gh, gw) else g0
+    if pos_grid is not None:
+        print(f"stage 3: position table {g0} x {g0} resampled to {gh} x {gw} in every step", flush=True)
+    student = Stage3Engine(make_config(dim, depth, patch, args.stride_size, *args.input_size, n_reg), device,
+                           pos_grid=pos_grid)
     student.load_timm(vit._state_dict)
     return student, teacher
 

@@ -40,7 +40,7 @@ extern "C" {
  *          attn.proj.weight [dim, dim], attn.proj.bias, ls1.gamma, norm2.weight, norm2.bias, mlp.fc1.weight [mlp, dim],
  *          mlp.fc1.bias, mlp.fc2.weight [dim, mlp], mlp.fc2.bias, ls2.gamma
  *   out[5 + 14 depth] norm.weight, out[6 + 14 depth] norm.bias, out[7 + 14 depth] = total floats (a multiple of 4).
- * `out` must hold 8 + 14 depth entries. */
+ * `out` must hold 8 + 14 depth entries.  dvt_s3_param_offsets_pos keeps pos_embed at the checkpoint's grid instead. */
 int dvt_s3_param_offsets(const DvtVitConfig* cfg, int64_t* out);
 
 /* Bytes of scratch for a step over `batch` images (every block's activations are kept). */
@@ -60,6 +60,43 @@ int dvt_s3_train_step(const DvtVitConfig* cfg, const float* params, float* grads
 int dvt_s3_train_slice(const DvtVitConfig* cfg, const float* params, float* grads, const float* img, const float* target,
                        float* feat_out, int batch, int norm_batch, void* work, int64_t work_bytes, float* loss_out,
                        void* stream);
+
+/* ---- a position table at another grid than the run's -------------------------------------------------------------
+ * timm (dynamic_img_size) resamples pos_embed in every forward -- F.interpolate(bicubic, antialias, align_corners=False) in
+ * fp32 on the square g0 x g0 patch part of the table, prefix rows carried over -- and autograd carries the gradient back to
+ * the checkpoint's table.  The map is linear and separable: per channel O = Wy P Wx^T.  The caller supplies the two tables,
+ * dense, on the device: wy [grid_h, g0], wx [grid_w, g0] (row = output position; taken from torch itself by
+ * dvt_amd.s3.pos_tables).  A table may be NULL when its axis keeps its length (g0 == grid_h resp. grid_w): the identity.
+ * Entries that are exactly zero are skipped and the remaining taps are summed in ascending order, one fma each: no atomics,
+ * no shared memory, two runs give the same bits.  dim % 4 == 0, every pointer 16-byte aligned.
+ *
+ * Forward: pos [has_cls + g0 g0, dim] -> out [has_cls + grid_h grid_w, dim]; x pass T[p, j] = sum_q wx[j, q] P[p, q] into
+ * tmp [g0, grid_w, dim], then y pass O[i, j] = sum_p wy[i, p] T[p, j] (ATen's order); the cls row is copied. */
+int dvt_pos_resample_fwd(const float* pos, float* out, const float* wy, const float* wx, float* tmp, int g0, int grid_h,
+                         int grid_w, int dim, int has_cls, void* stream);
+
+/* Transpose: dout [has_cls + grid_h grid_w, dim] -> dpos [has_cls + g0 g0, dim], ACCUMULATED:
+ * dT[p, j] = sum_i wy[i, p] dO[i, j] into tmp [g0, grid_w, dim], then dP[p, q] += sum_j wx[j, q] dT[p, j]; the cls row's
+ * gradient is added straight through. */
+int dvt_pos_resample_bwd(const float* dout, float* dpos, const float* wy, const float* wx, float* tmp, int g0, int grid_h,
+                         int grid_w, int dim, int has_cls, void* stream);
+
+/* The step with pos_embed kept at the CHECKPOINT's shape [1, pos_has_cls + g0 g0, dim] in all four arenas: the layout of
+ * dvt_s3_param_offsets with out[4] sized for g0 x g0 (g0 >= 1, else DVT_E_BADARG). */
+int dvt_s3_param_offsets_pos(const DvtVitConfig* cfg, int g0, int64_t* out);
+
+/* dvt_s3_workspace_bytes plus, when g0 x g0 is not the run's grid, the run-grid table, its gradient and the resample's
+ * intermediate.  -1 for g0 < 1. */
+int64_t dvt_s3_workspace_bytes_pos(const DvtVitConfig* cfg, int batch, int g0);
+
+/* dvt_s3_train_slice over that layout.  When g0 x g0 is the run's grid the tables are ignored and the call IS
+ * dvt_s3_train_slice.  Otherwise each call resamples `params`' table into the workspace for the token assembly, lets the
+ * assembly's backward add into a zeroed run-grid gradient there, and adds its transpose into `grads` (slices stay additive:
+ * the map is linear).  DVT_E_BADARG, before any pointer is touched: g0 < 1, a NULL table on an axis whose length is not g0,
+ * a workspace below dvt_s3_workspace_bytes_pos. */
+int dvt_s3_train_slice_pos(const DvtVitConfig* cfg, int g0, const float* wy, const float* wx, const float* params,
+                           float* grads, const float* img, const float* target, float* feat_out, int batch, int norm_batch,
+                           void* work, int64_t work_bytes, float* loss_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,13 @@ run them, attention over all s_pad keys); the teacher's forward (fp32 ViT + the 
 student's step) is not part of the timed step.
 
     python tools/bench_stage3.py [--dim 768 --depth 12 --img 518 --batch 64 --steps 3 --warmup 1]
+                                 [--input_size H W] [--stride_size S] [--pos_grid G0]
+
+`--input_size` / `--stride_size` set another geometry than `--img` square at stride 14; `--pos_grid G0` keeps the position
+table at G0 x G0 (37 for the DINOv2 checkpoints) and resamples it to the run's grid in every step, e.g.
+    --input_size 224 224 --pos_grid 37                     (16 x 16 tokens)
+    --stride_size 7 --pos_grid 37 --micro_batch 1          (73 x 73 tokens)
+The resample's launches are not matrix work and are not in the FLOPs; the JSON line names the grid and the table.
 """
 import argparse
 import json
@@ -40,13 +47,19 @@ def main():
     p.add_argument("--micro_batch", type=int, default=0)
     p.add_argument("--steps", type=int, default=3)
     p.add_argument("--warmup", type=int, default=1)
+    p.add_argument("--input_size", type=int, nargs=2, default=None, metavar=("H", "W"), help="default: --img square")
+    p.add_argument("--stride_size", type=int, default=14)
+    p.add_argument("--pos_grid", type=int, default=None,
+                   help="grid of the position table when it is not the run's (resampled in every step); default: the run's")
     a = p.parse_args()
     dev = torch.device("cuda:0")
-    cfg = s3.make_config(a.dim, a.depth, 14, 14, a.img, a.img)
-    eng = s3.Stage3Engine(cfg, dev)
-    eng.load_timm(random_state_dict(a.dim, a.depth, 14, 1 + cfg.grid_h * cfg.grid_w, well_conditioned=True))
+    H, W = a.input_size or (a.img, a.img)
+    cfg = s3.make_config(a.dim, a.depth, 14, a.stride_size, H, W)
+    eng = s3.Stage3Engine(cfg, dev, pos_grid=a.pos_grid)
+    n_pos = cfg.grid_h * cfg.grid_w if a.pos_grid is None else a.pos_grid ** 2
+    eng.load_timm(random_state_dict(a.dim, a.depth, 14, 1 + n_pos, well_conditioned=True))
     g = torch.Generator(device=dev).manual_seed(0)
-    img = torch.randn(a.batch, 3, a.img, a.img, device=dev, generator=g)
+    img = torch.randn(a.batch, 3, H, W, device=dev, generator=g)
     tgt = torch.randn(a.batch, cfg.grid_h, cfg.grid_w, a.dim, device=dev, generator=g)
     mb = a.micro_batch or None
     for _ in range(a.warmup):
@@ -60,7 +73,8 @@ def main():
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
     fl = step_flops(cfg, a.batch)
-    print(json.dumps({"bench": "stage3_student_step", "dim": a.dim, "depth": a.depth, "img": a.img, "batch": a.batch,
+    print(json.dumps({"bench": "stage3_student_step", "dim": a.dim, "depth": a.depth, "img": a.img if a.input_size is None else [H, W],
+                      "stride": a.stride_size, "grid": [cfg.grid_h, cfg.grid_w], "pos_grid": a.pos_grid, "batch": a.batch,
                       "slice": eng.slice_size(a.batch) if mb is None else mb, "ms_per_step": round(dt * 1e3, 2),
                       "images_per_s": round(a.batch / dt, 3), "tflop_per_step": round(fl / 1e12, 2),
                       "tflops": round(fl / dt / 1e12, 2), "fraction_of_fp32_peak": round(fl / dt / PEAK_FP32, 3),
