@@ -1201,3 +1201,32 @@ extern "C" int dvt_linear_bwd(const float* dy, const float* x, const float* w, f
   }
   return 0;
 }
+
+// ---- component entry points for tests (include/dvt_parts.h): forwarders only, no kernel and no launch of their own ----
+#include "../../include/dvt_parts.h"
+static_assert(sizeof(DvtPartsGemmEx) == 160, "DvtPartsGemmEx: explicit padding, mirrored by dvt_amd/_lib.py PartsGemmEx");
+
+extern "C" int dvt_parts_gemm_ex(const DvtPartsGemmEx* p, void* stream) {
+  if (!p || p->layout < 0 || p->layout > 2 || p->ldc < p->N || p->nb0 < 0 || p->nb1 < 0) return DVT_E_BADARG;
+  DvtGemmEx g{};
+  g.layout = p->layout;
+  g.A = p->A; g.B = p->B; g.C = p->C;
+  g.M = p->M; g.N = p->N; g.K = p->K;
+  g.lda = p->lda; g.ldb = p->ldb; g.ldc = p->ldc;
+  g.bias = p->bias;
+  g.colsum = p->colsum;
+  g.accumulate = p->accumulate;
+  g.nb0 = p->nb0; g.nb1 = p->nb1;
+  g.sA0 = p->sA0; g.sA1 = p->sA1; g.sB0 = p->sB0; g.sB1 = p->sB1; g.sC0 = p->sC0; g.sC1 = p->sC1;
+  g.smul = p->smul;
+  g.rowsub = p->rowsub;
+  g.oscale = p->oscale;
+  return dvt_gemm_f32_ex(&g, (hipStream_t)stream);  // (every check of its own runs before its launch)
+}
+
+extern "C" int dvt_parts_linear_big_epi(const float* x, const float* w, const float* b, float* y, int m, int n, int k, int epi,
+                                        const float* gamma, void* stream) {
+  if (epi < 0 || epi > 2) return DVT_E_BADARG;
+  if (epi == 0) return dvt_linear_fwd_big(x, w, b, y, m, n, k, (hipStream_t)stream);
+  return dvt_linear_fwd_big_epi(x, w, b, y, m, n, k, epi, gamma, (hipStream_t)stream);
+}

@@ -518,3 +518,106 @@ extern "C" int dvt_adamw_step(float* params, float* grads, float* m, float* v, i
   DVT_CHECK_LAUNCH();
   return 0;
 }
+
+// ---- component entry points for tests (include/dvt_parts.h): forwarders to THIS translation unit's copy of the dvt_s2_parts.h
+// kernels and to the kernels above; no kernel and no launch of their own, every check in front of the first launch ----
+#include "../../include/dvt_parts.h"
+
+namespace {
+bool parts_c_ok(int C) { return C == 384 || C == 768 || C == 1024; }
+bool parts_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+}  // namespace
+
+extern "C" int dvt_parts_lin_fwd(const float* x, const float* w, const float* b, float* y, int R, int n, int k, void* stream) {
+  s2_read_env();
+  if (!x || !w || !y || R <= 0 || n <= 0 || k <= 0 || (n & 3) || (k & 3)) return DVT_E_BADARG;
+  if (!(g_s2_big_fwd && dvt_linear_big_ok(R, n, k)) && (k % 64)) return DVT_E_BADARG;  // dvt_gemm_f32_ex: whole k-tiles
+  return lin_fwd(x, w, b, y, R, n, k, (hipStream_t)stream);
+}
+
+extern "C" int dvt_parts_lin_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, float* db, float* wT,
+                                 int R, int n, int k, void* stream) {
+  s2_read_env();
+  if (!dy || !x || !dw || !db || (dx && !w) || R <= 0 || n <= 0 || k <= 0) return DVT_E_BADARG;
+  if ((n % 64) || (k % 64) || (R % 32)) return DVT_E_BADARG;
+  // the 64 x 64 weight-gradient kernel reduces over whole 64-row tiles, and so does the layout-1 data gradient's operand
+  if ((R % 64) && !(g_s2_big_wgrad && dvt_linear_wgrad_big_ok(R, n, k))) return DVT_E_BADARG;
+  return lin_bwd(dy, x, w, dx, dw, db, R, n, k, (hipStream_t)stream, wT);
+}
+
+extern "C" int dvt_parts_attn_rows(int mode, const float* rowop, int ld_row, const float* keyop, int ld_key, const float* P,
+                                   const float* D, float* out, int batch, int heads, int T, int Tp, float scale, void* stream) {
+  if ((mode != 0 && mode != 1) || !rowop || !keyop || !out || batch < 1 || heads < 1 || Tp < AR_Q || (Tp % AR_Q) || T < 1 || T > Tp)
+    return DVT_E_BADARG;
+  if (ld_row < heads * 64 || ld_key < heads * 64 || (ld_key & 3) || !parts_al16(keyop) || (mode == 1 && (!P || !D)))
+    return DVT_E_BADARG;
+  if ((int64_t)(Tp / AR_Q) * heads * batch > 0x7fffffffLL) return DVT_E_BADARG;
+  const dim3 grid((Tp / AR_Q) * heads * batch), blk(256);
+  hipStream_t s = (hipStream_t)stream;
+  if (mode == 0)
+    hipLaunchKernelGGL(s2_attn_rows_kernel<0>, grid, blk, 0, s, rowop, ld_row, keyop, ld_key, (const float*)nullptr,
+                       (const float*)nullptr, out, heads, T, Tp, scale);
+  else
+    hipLaunchKernelGGL(s2_attn_rows_kernel<1>, grid, blk, 0, s, rowop, ld_row, keyop, ld_key, P, D, out, heads, T, Tp, scale);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dvt_parts_rowdot(const float* dO, const float* O, float* D, int R, int Tp, int C, void* stream) {
+  if (!dO || !O || !D || R < 1 || Tp < 1 || (R % Tp) || C < 64 || (C % 64) || !parts_al16(dO) || !parts_al16(O)) return DVT_E_BADARG;
+  hipLaunchKernelGGL(s2_rowdot_kernel, dim3(dvt_cdiv(R, 4)), dim3(256), 0, (hipStream_t)stream, dO, O, D, R, Tp, C);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dvt_parts_ln_bwd(int C, const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                                const float* dres, float* dx, float* dgamma, float* dbeta, int R, void* stream) {
+  if (!parts_c_ok(C) || !dy || !x || !mean || !rstd || !gamma || !dx || !dgamma || !dbeta || R < 1) return DVT_E_BADARG;
+  return ln_bwd(C, dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, R, (hipStream_t)stream);
+}
+
+extern "C" int dvt_parts_add_ln(int C, const float* a, int a_packed, const float* b, int b_is_pos, float* sum_out,
+                                const float* gamma, const float* beta, float* xn, float* mean, float* rstd, int T, int Tp, int R,
+                                float eps, void* stream) {
+  if (!parts_c_ok(C) || !a || !gamma || !beta || !xn || !mean || !rstd || T < 1 || Tp < T || R < 1 || (R % Tp) || !(eps > 0.f))
+    return DVT_E_BADARG;
+  return add_ln(C, a, a_packed, b, b_is_pos, sum_out, gamma, beta, xn, mean, rstd, T, Tp, R, eps, (hipStream_t)stream);
+}
+
+extern "C" int dvt_parts_gelu(const float* h, float* a, int64_t n4, int backward, void* stream) {
+  if (!h || !a || n4 < 1 || !parts_al16(h) || !parts_al16(a) || (backward != 0 && backward != 1)) return DVT_E_BADARG;
+  if (backward)
+    hipLaunchKernelGGL(s2_gelu_bwd_kernel, dim3(dvt_cdiv(n4, 256)), dim3(256), 0, (hipStream_t)stream, (const float4*)h, (float4*)a, n4);
+  else
+    hipLaunchKernelGGL(s2_gelu_kernel, dim3(dvt_cdiv(n4, 256)), dim3(256), 0, (hipStream_t)stream, (const float4*)h, (float4*)a, n4);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dvt_parts_softmax(const float* P, float* S, int T, int Tp, int64_t rows, float scale, int backward, void* stream) {
+  if (!S || Tp < 4 || (Tp & 3) || T < 1 || T > Tp || rows < 1 || !parts_al16(S) || (backward != 0 && backward != 1)) return DVT_E_BADARG;
+  if (backward && (!P || !parts_al16(P))) return DVT_E_BADARG;
+  if (backward)
+    hipLaunchKernelGGL(s2_softmax_bwd_kernel, dim3(dvt_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, P, S, Tp, rows, scale);
+  else
+    hipLaunchKernelGGL(s2_softmax_kernel, dim3(dvt_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, S, T, Tp, rows, scale);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dvt_parts_loss_rows(int C, const float* a, const float* b, const float* target, float* out, float* dout, float* acc,
+                                   int n_prefix, int T, int Tp, int R, int norm_batch, float* loss_out, int add, void* stream) {
+  if (!parts_c_ok(C) || !a || !target || !dout || !acc || !loss_out || (add && !b) || (add != 0 && add != 1)) return DVT_E_BADARG;
+  if (n_prefix < 0 || T <= n_prefix || Tp < T || R < 1 || (R % Tp) || norm_batch < R / Tp) return DVT_E_BADARG;
+  if (add) return loss_rows<true>(C, a, b, target, out, dout, acc, n_prefix, T, Tp, R, norm_batch, loss_out, (hipStream_t)stream);
+  return loss_rows<false>(C, a, nullptr, target, out, dout, acc, n_prefix, T, Tp, R, norm_batch, loss_out, (hipStream_t)stream);
+}
+
+extern "C" int dvt_parts_pos_grad(const float* dx, float* dpos, int batch, int T, int Tp, int C, void* stream) {
+  if (!dx || !dpos || batch < 1 || T < 1 || Tp < T || C < 4 || (C & 3) || !parts_al16(dx) || !parts_al16(dpos)) return DVT_E_BADARG;
+  const int64_t n = (int64_t)T * (C / 4);
+  hipLaunchKernelGGL(s2_pos_grad_kernel, dim3(dvt_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, (const float4*)dx, (float4*)dpos,
+                     batch, T, Tp, C / 4);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}

@@ -613,3 +613,83 @@ extern "C" int dvt_s3_train_slice_pos(const DvtVitConfig* cfg, int g0, const flo
   return run(cfg, params, grads, img, target, feat_out, batch, norm_batch, work, work_bytes, loss_out, (hipStream_t)stream, g0,
              wy, wx);
 }
+
+// ---- component entry points for tests (include/dvt_parts.h): forwarders to the kernels above; no kernel and no launch of their
+// own, every check in front of the launch ----
+#include "../../include/dvt_parts.h"
+
+namespace {
+bool parts_c_ok(int C) { return C == 384 || C == 768 || C == 1024; }
+// the fields the assembly / im2col kernels read, the rest zero
+int parts_cfg(DvtVitConfig* c, int dim, int n_prefix, int n_tokens, int s_pad, int pos_has_cls) {
+  if (dim < 4 || (dim & 3) || n_prefix < 0 || n_tokens <= n_prefix || s_pad < n_tokens || (pos_has_cls != 0 && pos_has_cls != 1))
+    return DVT_E_BADARG;
+  *c = DvtVitConfig{};
+  c->dim = dim;
+  c->n_prefix = n_prefix;
+  c->n_tokens = n_tokens;
+  c->s_pad = s_pad;
+  c->pos_has_cls = pos_has_cls;
+  return 0;
+}
+}  // namespace
+
+extern "C" int dvt_parts_ls_add_ln(int C, const float* a, const float* f, const float* ls, float* sum_out, const float* gamma,
+                                   const float* beta, float* xn, float* mean, float* rstd, int T, int Tp, int R, float eps,
+                                   void* stream) {
+  if (!parts_c_ok(C) || !a || (ls && !f) || !gamma || !beta || !xn || !mean || !rstd || T < 1 || Tp < T || R < 1 || (R % Tp) ||
+      !(eps > 0.f))
+    return DVT_E_BADARG;
+  return ls_add_ln(C, a, f, ls, sum_out, gamma, beta, xn, mean, rstd, T, Tp, R, eps, (hipStream_t)stream);
+}
+
+extern "C" int dvt_parts_ls_bwd(int C, const float* dy, const float* f, const float* ls, float* df, float* dls, int R, void* stream) {
+  if (!parts_c_ok(C) || !dy || !f || !ls || !df || !dls || R < 1) return DVT_E_BADARG;
+  return ls_bwd(C, dy, f, ls, df, dls, R, (hipStream_t)stream);
+}
+
+extern "C" int dvt_parts_s3_embed(const float* y, float* x, const float* prefix, const float* pos, int batch, int dim, int n_prefix,
+                                  int n_tokens, int s_pad, int pos_has_cls, void* stream) {
+  DvtVitConfig c;
+  S2_TRY(parts_cfg(&c, dim, n_prefix, n_tokens, s_pad, pos_has_cls));
+  if (!y || !x || !pos || (n_prefix > 0 && !prefix) || batch < 1 || !aligned16(y) || !aligned16(x) || !aligned16(prefix) || !aligned16(pos))
+    return DVT_E_BADARG;
+  hipLaunchKernelGGL(s3_embed_kernel, dim3(batch * s_pad), dim3(256), 0, (hipStream_t)stream, (const float4*)y, (float4*)x,
+                     (const float4*)prefix, (const float4*)pos, c);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dvt_parts_s3_embed_bwd(float* dx, float* dprefix, float* dpos, int batch, int dim, int n_prefix, int n_tokens,
+                                      int s_pad, int pos_has_cls, void* stream) {
+  DvtVitConfig c;
+  S2_TRY(parts_cfg(&c, dim, n_prefix, n_tokens, s_pad, pos_has_cls));
+  if (!dx || !dpos || (n_prefix > 0 && !dprefix) || batch < 1 || !aligned16(dx) || !aligned16(dprefix) || !aligned16(dpos))
+    return DVT_E_BADARG;
+  const int64_t n = (int64_t)n_tokens * (dim / 4);
+  hipLaunchKernelGGL(s3_embed_bwd_kernel, dim3(dvt_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, (float4*)dx, (float4*)dprefix,
+                     (float4*)dpos, batch, c);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dvt_parts_s3_im2col(const float* img, float* col, int batch, int patch, int stride, int img_h, int img_w, int grid_h,
+                                   int grid_w, int n_prefix, int s_pad, int k_patch, void* stream) {
+  if (!img || !col || batch < 1 || patch < 1 || stride < 1 || grid_h < 1 || grid_w < 1 || n_prefix < 0) return DVT_E_BADARG;
+  if ((grid_h - 1) * stride + patch > img_h || (grid_w - 1) * stride + patch > img_w) return DVT_E_BADARG;
+  if (s_pad < n_prefix + grid_h * grid_w || k_patch < 3 * patch * patch) return DVT_E_BADARG;
+  DvtVitConfig c{};
+  c.patch = patch;
+  c.stride = stride;
+  c.img_h = img_h;
+  c.img_w = img_w;
+  c.grid_h = grid_h;
+  c.grid_w = grid_w;
+  c.n_prefix = n_prefix;
+  c.n_tokens = n_prefix + grid_h * grid_w;
+  c.s_pad = s_pad;
+  c.k_patch = k_patch;
+  hipLaunchKernelGGL(s3_im2col_kernel, dim3(batch * s_pad), dim3(256), 0, (hipStream_t)stream, img, col, c);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}

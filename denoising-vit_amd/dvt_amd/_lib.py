@@ -134,8 +134,43 @@ class FitBuffers(C.Structure):
     ]
 
 
+class PartsGemmEx(C.Structure):
+    """include/dvt_parts.h: DvtPartsGemmEx (the component entry points the tests drive)."""
+    _fields_ = [
+        ("layout", C.c_int32),
+        ("pad0_", C.c_int32),
+        ("A", C.c_void_p),
+        ("B", C.c_void_p),
+        ("C", C.c_void_p),
+        ("M", C.c_int32),
+        ("N", C.c_int32),
+        ("K", C.c_int32),
+        ("lda", C.c_int32),
+        ("ldb", C.c_int32),
+        ("ldc", C.c_int32),
+        ("bias", C.c_void_p),
+        ("colsum", C.c_void_p),
+        ("accumulate", C.c_int32),
+        ("nb0", C.c_int32),
+        ("nb1", C.c_int32),
+        ("pad1_", C.c_int32),
+        ("sA0", C.c_int64),
+        ("sA1", C.c_int64),
+        ("sB0", C.c_int64),
+        ("sB1", C.c_int64),
+        ("sC0", C.c_int64),
+        ("sC1", C.c_int64),
+        ("smul", C.c_void_p),
+        ("rowsub", C.c_void_p),
+        ("oscale", C.c_float),
+        ("pad2_", C.c_int32),
+    ]
+
+
 _P = C.c_void_p
 _I = C.c_int
+_F = C.c_float
+_L = C.c_int64
 _SIGNATURES = {
     # name: (restype, argtypes)
     "dvt_abi_version": (_I, []),
@@ -163,6 +198,24 @@ _SIGNATURES = {
     "dvt_tune_set": (_I, [_I, _I]),
     "dvt_prof_enable": (_I, [C.c_uint]),
     "dvt_prof_collect": (_I, [_I, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    # include/dvt_parts.h: component entry points for tests
+    "dvt_parts_gemm_ex": (_I, [C.POINTER(PartsGemmEx), _P]),
+    "dvt_parts_linear_big_epi": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "dvt_parts_lin_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "dvt_parts_lin_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "dvt_parts_attn_rows": (_I, [_I, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "dvt_parts_rowdot": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "dvt_parts_ln_bwd": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "dvt_parts_add_ln": (_I, [_I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
+    "dvt_parts_gelu": (_I, [_P, _P, _L, _I, _P]),
+    "dvt_parts_softmax": (_I, [_P, _P, _I, _I, _L, _F, _I, _P]),
+    "dvt_parts_loss_rows": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "dvt_parts_pos_grad": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "dvt_parts_ls_add_ln": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
+    "dvt_parts_ls_bwd": (_I, [_I, _P, _P, _P, _P, _P, _I, _P]),
+    "dvt_parts_s3_embed": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "dvt_parts_s3_embed_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "dvt_parts_s3_im2col": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
 }
 
 PROBES = {"adam": 0, "vit_gemm": 1, "vit_attn": 2, "fit_gemm": 3, "grid": 4, "fit_rows": 5}
