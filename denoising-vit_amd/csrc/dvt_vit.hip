@@ -33,6 +33,7 @@
 
 #include "../../include/dvt_vit.h"
 #include "dvt_common.h"
+#include "dvt_ln_row.h"
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
@@ -1665,42 +1666,63 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   const float4* xr = reinterpret_cast<const float4*>(x + in_row * dim);
   const int nq = dim >> 2;
   float4 v[NV];
-  float sum = 0.f;
+  float mean, rstd;
+  ln_row_stats<NV>(xr, nq, dim, eps, lane, v, mean, rstd);
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int q = lane + 64 * i;
     if (q < nq) {
-      v[i] = xr[q];
-      sum += v[i].x + v[i].y + v[i].z + v[i].w;
-    }
-  }
-  const float mean = wave_sum(sum) / (float)dim;
-  float var = 0.f;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int q = lane + 64 * i;
-    if (q < nq) {
-      const float a = v[i].x - mean, bq = v[i].y - mean, cq = v[i].z - mean, d = v[i].w - mean;
-      var += a * a + bq * bq + cq * cq + d * d;
-    }
-  }
-  const float rstd = rsqrtf(wave_sum(var) / (float)dim + eps);
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int q = lane + 64 * i;
-    if (q < nq) {
-      const float4 ww = reinterpret_cast<const float4*>(w)[q];
-      const float4 bb = reinterpret_cast<const float4*>(b)[q];
-      const float o0 = (v[i].x - mean) * rstd * ww.x + bb.x, o1 = (v[i].y - mean) * rstd * ww.y + bb.y;
-      const float o2 = (v[i].z - mean) * rstd * ww.z + bb.z, o3 = (v[i].w - mean) * rstd * ww.w + bb.w;
+      const float4 o = ln_row_piece(v[i], mean, rstd, reinterpret_cast<const float4*>(w)[q], reinterpret_cast<const float4*>(b)[q]);
       if (FINAL) {
-        reinterpret_cast<float4*>(y_f32 + (size_t)row * dim)[q] = make_float4(o0, o1, o2, o3);
+        reinterpret_cast<float4*>(y_f32 + (size_t)row * dim)[q] = o;
       } else {
         uint2 pk;
-        pk.x = pack2(o0, o1);
-        pk.y = pack2(o2, o3);
+        pk.x = pack2(o.x, o.y);
+        pk.y = pack2(o.z, o.w);
         reinterpret_cast<uint2*>(y_bf16 + (size_t)row * dim)[q] = pk;
       }
+    }
+  }
+}
+
+// The tap of dvt_vit_forward*_taps: the residual rows of x [batch * s_pad, dim] after one block, prefix rows to `prefix`
+// [batch, n_prefix, dim] (NULL: dropped), patch rows NHWC to `feat` [batch, n_tokens - n_prefix, dim]; one wave per token row,
+// rows = batch * n_tokens (the pad rows behind n_tokens and the phantom rows are never addressed).  NORM: the final LayerNorm
+// of layernorm_kernel<true> / layernorm_f32_kernel<true> (ln_row_stats / ln_row_piece); else the rows as they are.
+template <bool NORM, int NV>
+__global__ __launch_bounds__(256) void tap_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                  const float* __restrict__ b, float* __restrict__ feat,
+                                                  float* __restrict__ prefix, int rows, int dim, float eps, int s_pad,
+                                                  int n_tokens, int n_prefix) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const int bb = row / n_tokens, s = row - bb * n_tokens;
+  float* y;
+  if (s < n_prefix) {
+    if (prefix == nullptr) return;
+    y = prefix + ((size_t)bb * n_prefix + s) * dim;
+  } else {
+    y = feat + ((size_t)bb * (n_tokens - n_prefix) + (s - n_prefix)) * dim;
+  }
+  const float4* xr = reinterpret_cast<const float4*>(x + ((size_t)bb * s_pad + s) * dim);
+  const int nq = dim >> 2;
+  if (NORM) {
+    float4 v[NV];
+    float mean, rstd;
+    ln_row_stats<NV>(xr, nq, dim, eps, lane, v, mean, rstd);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int q = lane + 64 * i;
+      if (q < nq)
+        reinterpret_cast<float4*>(y)[q] =
+            ln_row_piece(v[i], mean, rstd, reinterpret_cast<const float4*>(w)[q], reinterpret_cast<const float4*>(b)[q]);
+    }
+  } else {  // (slot by slot: a row parked in an array here is demoted to LDS / scratch by the compiler)
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int q = lane + 64 * i;
+      if (q < nq) reinterpret_cast<float4*>(y)[q] = xr[q];
     }
   }
 }
@@ -3084,12 +3106,47 @@ extern "C" int dvt_vit_attention_x3_presplit(const void* scratch, void* out, int
   return 0;
 }
 
-extern "C" int dvt_vit_forward(const DvtVitConfig* c, const DvtVitWeights* w, const float* img,
-                               float* feat, int batch, int n_blocks, void* workspace,
-                               void* stream) {
+// Host-side check of a tap list (include/dvt_vit.h), shared by the three tapped forwards: pure arithmetic on the two host
+// structs, before any device pointer is looked at.
+int dvt_vit_check_taps(const DvtVitConfig* c, const DvtVitTaps* t) {
+  if (!c || !t || t->n_taps < 1 || t->n_taps > DVT_VIT_MAX_TAPS) return DVT_E_BADARG;
+  for (int i = 0; i < t->n_taps; ++i) {
+    if (t->block[i] < 0 || t->block[i] >= c->depth || (i > 0 && t->block[i] <= t->block[i - 1])) return DVT_E_BADARG;
+    if (!t->feat[i] || (t->prefix[i] && c->n_prefix <= 0)) return DVT_E_BADARG;
+  }
+  return 0;
+}
+
+// One tap: the token rows of x after a block -> feat (patch rows, NHWC) and prefix (NULL: dropped); 4 register slots up to
+// dim 1024, 6 above, as launch_final_norm.
+int dvt_vit_launch_tap(const float* x, const DvtVitConfig* c, const float* norm_w, const float* norm_b, float* feat,
+                       float* prefix, int batch, int norm, hipStream_t s) {
+  const int rows = batch * c->n_tokens;
+  const dim3 grid(dvt_cdiv(rows, 4)), block(256);
+#define DVT_TAP(NORM, NV)                                                                                                  \
+  hipLaunchKernelGGL((tap_kernel<NORM, NV>), grid, block, 0, s, x, norm_w, norm_b, feat, prefix, rows, c->dim, c->ln_eps, \
+                     c->s_pad, c->n_tokens, c->n_prefix)
+  if (c->dim <= 1024) {
+    if (norm) DVT_TAP(true, 4);
+    else DVT_TAP(false, 4);
+  } else {
+    if (norm) DVT_TAP(true, 6);
+    else DVT_TAP(false, 6);
+  }
+#undef DVT_TAP
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int64_t dvt_vit_taps_struct_size(void) { return (int64_t)sizeof(DvtVitTaps); }
+
+// dvt_vit_forward (taps == NULL: n_blocks blocks, the final LayerNorm into feat) and dvt_vit_forward_taps (feat == NULL:
+// the blocks up to the last tap, one tap launch behind every tapped block) are the same launches in the same order.
+static int vit_forward_run(const DvtVitConfig* c, const DvtVitWeights* w, const float* img, float* feat,
+                           const DvtVitTaps* taps, int batch, int n_blocks, void* workspace, void* stream) {
   int rc = check_vit_cfg(c);
   if (rc) return rc;
-  if (!w || !img || !feat || !workspace || batch <= 0 || n_blocks < 0 || n_blocks > c->depth)
+  if (!w || !img || (!feat && !taps) || !workspace || batch <= 0 || n_blocks < 0 || n_blocks > c->depth)
     return DVT_E_BADARG;
   hipStream_t s = (hipStream_t)stream;
   VitWork k;
@@ -3133,6 +3190,7 @@ extern "C" int dvt_vit_forward(const DvtVitConfig* c, const DvtVitWeights* w, co
   if (fuse_ln) {
     DVT_TRY(dvt_vit_ln_cast_stats(k.x, k.xb, k.stats, T, D, c->ln_eps, s));
   }
+  int tap = 0;
   bool log2q = g_vit_attn_log2q != 0;
 #ifdef DVT_LAB
   log2q = log2q && g_vit_attn_variant == 2 && g_vit_attn_mask == 15;  // (the superseded kernels and schedule masks take q as it is)
@@ -3192,13 +3250,32 @@ extern "C" int dvt_vit_forward(const DvtVitConfig* c, const DvtVitWeights* w, co
       finalize_stats();
       DVT_CHECK_LAUNCH();
     }
+    if (taps && tap < taps->n_taps && l == taps->block[tap]) {  // (the fc2 epilogue of a tapped inner block has written xb and the partials too: x is
+      // stored before either, the same bits with or without them)
+      DVT_TRY(dvt_vit_launch_tap(k.x, c, w->norm_w, w->norm_b, taps->feat[tap], taps->prefix[tap], batch, taps->norm, s));
+      ++tap;
+    }
   }
 #undef DVT_TRY
+  if (taps) return 0;
   // final LayerNorm, drop cls/pad rows, NHWC fp32 straight into the feature store
   const int out_rows = batch * (c->n_tokens - c->n_prefix);
   launch_final_norm(k.x, w->norm_w, w->norm_b, feat, out_rows, D, c->ln_eps, c->s_pad, c->n_tokens, c->n_prefix, s);
   DVT_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int dvt_vit_forward(const DvtVitConfig* c, const DvtVitWeights* w, const float* img,
+                               float* feat, int batch, int n_blocks, void* workspace,
+                               void* stream) {
+  return vit_forward_run(c, w, img, feat, nullptr, batch, n_blocks, workspace, stream);
+}
+
+extern "C" int dvt_vit_forward_taps(const DvtVitConfig* c, const DvtVitWeights* w, const float* img, const DvtVitTaps* taps,
+                                    int batch, void* workspace, void* stream) {
+  const int rc = dvt_vit_check_taps(c, taps);
+  if (rc) return rc;
+  return vit_forward_run(c, w, img, nullptr, taps, batch, taps->block[taps->n_taps - 1] + 1, workspace, stream);
 }
 
 // The forward plus the final-normed cls row of every image: cls [batch, dim] fp32.  The patch tokens are the plain

@@ -14,6 +14,7 @@
 
 #include "../../include/dvt_vit.h"
 #include "dvt_common.h"
+#include "dvt_ln_row.h"
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef unsigned short bf16_t;
@@ -36,6 +37,10 @@ extern "C" int64_t dvt_vit_attention_x3_scratch_bytes(int batch, int heads, int 
 extern "C" int dvt_vit_gemm_gelu_x3(const void* a, const void* w, const float* b, void* out3, int m, int n, int k, void* stream);
 extern "C" int dvt_vit_gemm_qkv_x3(const void* a, const void* w, const float* b, void* scratch, int m, int dim, int heads,
                                    int s_pad, int batch, int k, void* stream);
+
+int dvt_vit_check_taps(const DvtVitConfig* c, const DvtVitTaps* t);  // dvt_vit.hip: the tap list's host check ...
+int dvt_vit_launch_tap(const float* x, const DvtVitConfig* c, const float* norm_w, const float* norm_b, float* feat,
+                       float* prefix, int batch, int norm, hipStream_t s);  // ... and the tap kernel's launch
 
 namespace {
 
@@ -185,33 +190,13 @@ __global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* __restr
   const float4* xr = reinterpret_cast<const float4*>(x + in_row * dim);
   const int nq = dim >> 2;
   float4 v[NV];
-  float sum = 0.f;
+  float mean, rstd;
+  ln_row_stats<NV>(xr, nq, dim, eps, lane, v, mean, rstd);
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int q = lane + 64 * i;
     if (q < nq) {
-      v[i] = xr[q];
-      sum += v[i].x + v[i].y + v[i].z + v[i].w;
-    }
-  }
-  const float mean = wave_sum(sum) / (float)dim;
-  float var = 0.f;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int q = lane + 64 * i;
-    if (q < nq) {
-      const float a = v[i].x - mean, bq = v[i].y - mean, cq = v[i].z - mean, d = v[i].w - mean;
-      var += a * a + bq * bq + cq * cq + d * d;
-    }
-  }
-  const float rstd = rsqrtf(wave_sum(var) / (float)dim + eps);
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int q = lane + 64 * i;
-    if (q < nq) {
-      const float4 ww = reinterpret_cast<const float4*>(w)[q], bb = reinterpret_cast<const float4*>(b)[q];
-      const float4 o = make_float4((v[i].x - mean) * rstd * ww.x + bb.x, (v[i].y - mean) * rstd * ww.y + bb.y,
-                                   (v[i].z - mean) * rstd * ww.z + bb.z, (v[i].w - mean) * rstd * ww.w + bb.w);
+      const float4 o = ln_row_piece(v[i], mean, rstd, reinterpret_cast<const float4*>(w)[q], reinterpret_cast<const float4*>(b)[q]);
       if constexpr (SPLIT)
         store_split4<0>(reinterpret_cast<bf16_t*>(y) + (size_t)row * 3 * dim, dim, q * 4, o);
       else
@@ -477,9 +462,10 @@ extern "C" int dvt_vit_linear_f32x3(const float* x, const void* w3, const float*
 // The fp32 forward with every linear layer as ONE bf16 GEMM over the K-concatenated split operands (3 x the bf16 flops
 // on the 2.5 PF/s pipe instead of the 157 TF/s fp32 one); LayerNorm, attention (fp32 MFMA), GELU, residual stream fp32
 // as in dvt_vit_forward_f32.  `h_w`: matrices = bf16 [out, 3 * in] from dvt_vit_split3(weights = 1); vectors fp32.
-extern "C" int dvt_vit_forward_f32x3(const DvtVitConfig* c, const DvtVitWeights* w, const float* img, float* feat,
-                                     int batch, int n_blocks, void* workspace, void* stream) {
-  if (!c || !w || !img || !feat || !workspace || batch <= 0 || n_blocks < 0 || n_blocks > c->depth)
+// (taps == NULL: the plain forward into feat; feat == NULL: the tapped one -- the same launches, see dvt_vit.hip)
+static int vit_forward_f32x3_run(const DvtVitConfig* c, const DvtVitWeights* w, const float* img, float* feat,
+                                 const DvtVitTaps* taps, int batch, int n_blocks, void* workspace, void* stream) {
+  if (!c || !w || !img || (!feat && !taps) || !workspace || batch <= 0 || n_blocks < 0 || n_blocks > c->depth)
     return DVT_E_BADARG;
   if (c->s_pad % 128 || c->dim % 128 || c->heads * 64 != c->dim || c->k_patch % 64 || c->mlp_dim % 128) return DVT_E_BADARG;
   // the split epilogues exist for the GELU MLP only, and the split LayerNorm holds a row in four register slots: the SwiGLU
@@ -509,6 +495,7 @@ extern "C" int dvt_vit_forward_f32x3(const DvtVitConfig* c, const DvtVitWeights*
     if (hipMemsetAsync((char*)k.a3 + (size_t)T * 3 * D * 2, 0, (size_t)(Tg - T) * 3 * D * 2, s) != hipSuccess)
       return DVT_E_BADARG;
   }
+  int tap = 0;
   for (int l = 0; l < n_blocks; ++l) {
     const DvtVitBlockWeights& bw = w->blocks[l];
     hipLaunchKernelGGL((layernorm_f32_kernel<false, true>), dim3(dvt_cdiv(T, 4)), dim3(256), 0, s, k.x, bw.norm1_w,
@@ -538,13 +525,30 @@ extern "C" int dvt_vit_forward_f32x3(const DvtVitConfig* c, const DvtVitWeights*
       DVT_TRY(dvt_vit_gemm_gelu_x3(k.a3, bw.fc1_w, bw.fc1_b, k.h3, Tg, c->mlp_dim, 3 * D, stream));
     }
     DVT_TRY(dvt_vit_gemm_residual(k.h3, bw.fc2_w, bw.fc2_b, bw.ls2, k.x, Tg, D, 3 * c->mlp_dim, stream));
+    if (taps && tap < taps->n_taps && l == taps->block[tap]) {
+      DVT_TRY(dvt_vit_launch_tap(k.x, c, w->norm_w, w->norm_b, taps->feat[tap], taps->prefix[tap], batch, taps->norm, s));
+      ++tap;
+    }
   }
 #undef DVT_TRY
+  if (taps) return 0;
   const int out_rows = batch * (c->n_tokens - c->n_prefix);
   hipLaunchKernelGGL(layernorm_f32_kernel<true>, dim3(dvt_cdiv(out_rows, 4)), dim3(256), 0, s, k.x, w->norm_w,
                      w->norm_b, feat, out_rows, D, c->ln_eps, c->s_pad, c->n_tokens, c->n_prefix);
   DVT_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int dvt_vit_forward_f32x3(const DvtVitConfig* c, const DvtVitWeights* w, const float* img, float* feat,
+                                     int batch, int n_blocks, void* workspace, void* stream) {
+  return vit_forward_f32x3_run(c, w, img, feat, nullptr, batch, n_blocks, workspace, stream);
+}
+
+extern "C" int dvt_vit_forward_f32x3_taps(const DvtVitConfig* c, const DvtVitWeights* w, const float* img,
+                                          const DvtVitTaps* taps, int batch, void* workspace, void* stream) {
+  const int rc = dvt_vit_check_taps(c, taps);
+  if (rc) return rc;
+  return vit_forward_f32x3_run(c, w, img, nullptr, taps, batch, taps->block[taps->n_taps - 1] + 1, workspace, stream);
 }
 
 extern "C" int dvt_vit_attention_f32(const float* qkv, float* out, int batch, int heads, int s_pad, int n_valid,
@@ -568,9 +572,9 @@ extern "C" int dvt_vit_im2col_f32(const DvtVitConfig* c, const float* img, float
   return 0;
 }
 
-extern "C" int dvt_vit_forward_f32(const DvtVitConfig* c, const DvtVitWeights* w, const float* img, float* feat,
-                                   int batch, int n_blocks, void* workspace, void* stream) {
-  if (!c || !w || !img || !feat || !workspace || batch <= 0 || n_blocks < 0 || n_blocks > c->depth)
+static int vit_forward_f32_run(const DvtVitConfig* c, const DvtVitWeights* w, const float* img, float* feat,
+                               const DvtVitTaps* taps, int batch, int n_blocks, void* workspace, void* stream) {
+  if (!c || !w || !img || (!feat && !taps) || !workspace || batch <= 0 || n_blocks < 0 || n_blocks > c->depth)
     return DVT_E_BADARG;
   if (c->s_pad % 32 || c->dim % 64 || c->dim > 1536 || c->heads * 64 != c->dim || c->k_patch % 4) return DVT_E_BADARG;
   if (c->mlp_kind != DVT_VIT_MLP_GELU && c->mlp_kind != DVT_VIT_MLP_SWIGLU) return DVT_E_BADARG;
@@ -593,6 +597,7 @@ extern "C" int dvt_vit_forward_f32(const DvtVitConfig* c, const DvtVitWeights* w
   hipLaunchKernelGGL(embed_f32_kernel, dim3(T), dim3(256), 0, s, (const float4*)k.tmp, (float4*)k.x,
                      (const float4*)w->cls_token, (const float4*)w->pos_embed, *c);
   DVT_CHECK_LAUNCH();
+  int tap = 0;
   for (int l = 0; l < n_blocks; ++l) {
     const DvtVitBlockWeights& bw = w->blocks[l];
     launch_ln_f32(k.x, bw.norm1_w, bw.norm1_b, k.xn, T, D, c->ln_eps, s);
@@ -640,12 +645,29 @@ extern "C" int dvt_vit_forward_f32(const DvtVitConfig* c, const DvtVitWeights* w
                          (const float4*)bw.ls2, nqD, D / 4);
       DVT_CHECK_LAUNCH();
     }
+    if (taps && tap < taps->n_taps && l == taps->block[tap]) {
+      DVT_TRY(dvt_vit_launch_tap(k.x, c, w->norm_w, w->norm_b, taps->feat[tap], taps->prefix[tap], batch, taps->norm, s));
+      ++tap;
+    }
   }
 #undef DVT_TRY
+  if (taps) return 0;
   const int out_rows = batch * (c->n_tokens - c->n_prefix);
   launch_final_ln_f32(k.x, w->norm_w, w->norm_b, feat, out_rows, D, c->ln_eps, c->s_pad, c->n_tokens, c->n_prefix, s);
   DVT_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int dvt_vit_forward_f32(const DvtVitConfig* c, const DvtVitWeights* w, const float* img, float* feat,
+                                   int batch, int n_blocks, void* workspace, void* stream) {
+  return vit_forward_f32_run(c, w, img, feat, nullptr, batch, n_blocks, workspace, stream);
+}
+
+extern "C" int dvt_vit_forward_f32_taps(const DvtVitConfig* c, const DvtVitWeights* w, const float* img,
+                                        const DvtVitTaps* taps, int batch, void* workspace, void* stream) {
+  const int rc = dvt_vit_check_taps(c, taps);
+  if (rc) return rc;
+  return vit_forward_f32_run(c, w, img, nullptr, taps, batch, taps->block[taps->n_taps - 1] + 1, workspace, stream);
 }
 
 // dvt_vit_forward_f32 plus the final-normed cls row of every image (cls [batch, dim] fp32), read from the same residual stream.

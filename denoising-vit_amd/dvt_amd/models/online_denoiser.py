@@ -106,11 +106,15 @@ class Denoiser(nn.Module):
 
     def forward(self, x, return_dict=False, return_channel_first=False, return_class_token=False, norm=True):
         class_tokens = None
+        # without a ViT there is no class token to return: the reference's assert (online_denoiser.py:101-103), before any work
+        assert self.vit is not None or return_dict or not return_class_token, "return_class_token=True needs a vit"
         if self.vit is not None:
-            if return_class_token:
-                raise NotImplementedError("class tokens are not produced by the HIP extractor")
-            with torch.no_grad():
-                vit_outputs = self.vit.get_intermediate_layers(x, n=[self.vit.last_layer_index], norm=norm)
+            with torch.no_grad():  # online_denoiser.py:70-84
+                vit_outputs = self.vit.get_intermediate_layers(x, n=[self.vit.last_layer_index],
+                                                               return_prefix_tokens=return_class_token, norm=norm)
+                if return_class_token:
+                    vit_outputs = vit_outputs[-1]
+                    class_tokens = vit_outputs[1][:, 0]
                 original_feats = vit_outputs[0].permute(0, 2, 3, 1)
                 x = original_feats
         else:
@@ -122,7 +126,10 @@ class Denoiser(nn.Module):
         if return_channel_first:
             y = y.permute(0, 3, 1, 2)
         if return_dict:
-            return {"denoised_feats": y, "original_feats": original_feats.detach(), "class_tokens": class_tokens}
+            return {"denoised_feats": y, "original_feats": original_feats.detach(),
+                    "class_tokens": class_tokens.detach() if class_tokens is not None else None}
+        if return_class_token:
+            return y, class_tokens
         return y
 
     def training_step(self, original_feats: torch.Tensor, denoised_feats: torch.Tensor,

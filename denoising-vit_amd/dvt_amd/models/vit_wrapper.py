@@ -18,7 +18,10 @@ Differences forced by the environment (documented in DESIGN.md):
   * the stride override (vit_wrapper.py:78-91) is honoured by the im2col kernel, but a
     grid other than the checkpoint's own is served by resampling pos_embed on the host (timm's
     resample_abs_pos_embed restated); the *_reg4_* models carry 4 register tokens (prefix tokens
-    are stripped from the returned map like timm's `return_prefix_tokens=False`).
+    are stripped from the returned map like timm's `return_prefix_tokens=False`, and returned beside
+    it, cls first, with `return_prefix_tokens=True`).
+  * several `n` indices, `return_prefix_tokens` and `norm=False` come from ONE forward of the extractor
+    (HipViT.forward_taps); `forward(x)` is the final-normed cls token.
 """
 from __future__ import annotations
 
@@ -189,13 +192,28 @@ class PretrainedViTWrapper(nn.Module):
 
     def features_nhwc(self, x: torch.Tensor, layer_index: int | None = None,
                       out: torch.Tensor | None = None, max_batch: int = 128,
-                      dtype: str | None = None, matmul: str = "highest") -> torch.Tensor:
+                      dtype: str | None = None, matmul: str = "highest", return_cls: bool = False):
         """Fast path used by the stage-1 driver: NHWC fp32 patch-token map, optionally written
         straight into a slice of the feature store (no NCHW round trip).  `matmul` "high" (float32 only): linear
-        layers through bf16x3 (dvt_amd.vit.HipViT)."""
+        layers through bf16x3 (dvt_amd.vit.HipViT).  return_cls: -> (map, cls [B, dim]), the final-normed cls token of the
+        same forward (HipViT.forward_features)."""
         idx = self.last_layer_index if layer_index is None else layer_index
         return self._engine(x.device, dtype, matmul).forward_features(x.float(), n_blocks=idx + 1, out=out,
-                                                                      max_batch=max_batch)
+                                                                      max_batch=max_batch, return_cls=return_cls)
+
+    def tap_indices(self, n: Union[int, List[int], Tuple[int]]) -> Tuple[List[int], List[int]]:
+        """`n` of get_intermediate_layers -> (the block index of every returned entry, in the order of `n`; the unique
+        ascending taps the one forward runs).  An int means the last n blocks; negative indices count from the end."""
+        depth = self.num_blocks
+        if isinstance(n, int):
+            if not 1 <= n <= depth:
+                raise ValueError(f"n={n}: a model of {depth} blocks has 1 to {depth} last blocks")
+            order = list(range(depth - n, depth))
+        else:
+            order = [int(i) if int(i) >= 0 else depth + int(i) for i in n]
+            if not order or any(i < 0 or i >= depth for i in order):
+                raise ValueError(f"n={list(n)}: block indices of a model of {depth} blocks lie in [-{depth}, {depth})")
+        return order, sorted(set(order))
 
     def get_intermediate_layers(
         self,
@@ -205,19 +223,31 @@ class PretrainedViTWrapper(nn.Module):
         return_prefix_tokens: bool = False,
         norm: bool = True,
     ) -> List[torch.Tensor]:
-        if return_prefix_tokens or not norm:
-            raise NotImplementedError("return_prefix_tokens / norm=False are not on the DVT path")
-        if isinstance(n, int):
-            indices = list(range(self.num_blocks - n, self.num_blocks))
-        else:
-            indices = [i if i >= 0 else self.num_blocks + i for i in n]
-        outs = []
-        for i in indices:
-            f = self.features_nhwc(x, i)  # [B, gh, gw, C]
+        """timm's `get_intermediate_layers` / `forward_intermediates` (vit_wrapper.py:122-143) from ONE forward of the HIP
+        extractor: the blocks up to the highest index run once and every asked layer is tapped on the way
+        (HipViT.forward_taps).  `n`: an int = the last n blocks, or block indices (negatives count from the end).  The results
+        come back in the order of `n`, a repeated index as the same tensor; timm's own order for an unsorted list is not
+        pinned here (timm is absent).  reshape=True: NCHW as a permuted view of the NHWC map, else [B, L, C].
+        return_prefix_tokens=True: a list of (features, prefix_tokens [B, n_prefix, C]), all prefix rows: cls, then the
+        registers.  norm=False: the rows before the final LayerNorm."""
+        order, taps = self.tap_indices(n)
+        eng = self._engine(x.device)
+        res = {}
+        step = _vit.DVT_VIT_MAX_TAPS  # (more layers than one call taps: the deeper groups start again from the patch embedding)
+        for g in range(0, len(taps), step):
+            got = eng.forward_taps(x.float(), taps[g:g + step], norm=norm, return_prefix=return_prefix_tokens)
+            res.update(zip(taps[g:g + step], got))
+        shaped = {}
+        for i in taps:
+            f, p = res[i] if return_prefix_tokens else (res[i], None)  # f: [B, gh, gw, C]
             # timm returns NCHW (`output_fmt="NCHW"`); a permuted view keeps the driver's
             # `.permute(0, 2, 3, 1)` (main_img_denoising.py:323) free
-            outs.append(f.permute(0, 3, 1, 2) if reshape else f.reshape(f.shape[0], -1, f.shape[-1]))
-        return outs
+            f = f.permute(0, 3, 1, 2) if reshape else f.reshape(f.shape[0], -1, f.shape[-1])
+            shaped[i] = (f, p) if return_prefix_tokens else f
+        return [shaped[i] for i in order]
 
-    def forward(self, x: torch.Tensor):
-        raise NotImplementedError("classification forward is not on the stage-1 path")
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """The final-normed cls token [B, dim]: timm's forward_head(forward_features(x)) at num_classes=0 and
+        global_pool="token", the configuration of all fourteen built ids -- restated from timm's source, not pinned against
+        it (timm is absent)."""
+        return self.features_nhwc(x, return_cls=True)[1]

@@ -41,7 +41,17 @@ class VitWeights(C.Structure):
                                           "norm_b")] + [("blocks", VitBlockWeights * DVT_VIT_MAX_DEPTH)]
 
 
+DVT_VIT_MAX_TAPS = 16
+
+
+class VitTaps(C.Structure):
+    """include/dvt_vit.h: DvtVitTaps, the tap list of dvt_vit_forward*_taps."""
+    _fields_ = [("n_taps", C.c_int32), ("norm", C.c_int32), ("block", C.c_int32 * DVT_VIT_MAX_TAPS),
+                ("feat", C.c_void_p * DVT_VIT_MAX_TAPS), ("prefix", C.c_void_p * DVT_VIT_MAX_TAPS)]
+
+
 _P, _I = C.c_void_p, C.c_int
+_TAPS_SIG = (_I, [C.POINTER(VitConfig), C.POINTER(VitWeights), _P, C.POINTER(VitTaps), _I, _P, _P])
 _lib.register_signatures({
     "dvt_vit_config": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(VitConfig)]),
     "dvt_vit_config_reg": (_I, [_I, _I, _I, _I, _I, _I, _I, C.POINTER(VitConfig)]),
@@ -76,6 +86,10 @@ _lib.register_signatures({
     "dvt_vit_forward_cls": (_I, [C.POINTER(VitConfig), C.POINTER(VitWeights), _P, _P, _P, _I, _I, _P, _P]),
     "dvt_vit_forward_f32_cls": (_I, [C.POINTER(VitConfig), C.POINTER(VitWeights), _P, _P, _P, _I, _I, _P, _P]),
     "dvt_vit_forward_f32x3_cls": (_I, [C.POINTER(VitConfig), C.POINTER(VitWeights), _P, _P, _P, _I, _I, _P, _P]),
+    "dvt_vit_taps_struct_size": (C.c_int64, []),
+    "dvt_vit_forward_taps": _TAPS_SIG,
+    "dvt_vit_forward_f32_taps": _TAPS_SIG,
+    "dvt_vit_forward_f32x3_taps": _TAPS_SIG,
     "dvt_vit_im2col": (_I, [C.POINTER(VitConfig), _P, _P, _I, _P]),
     "dvt_vit_im2col_f32": (_I, [C.POINTER(VitConfig), _P, _P, _I, _P]),
     "dvt_vit_ln_cast_stats": (_I, [_P, _P, _P, _I, _I, C.c_float, _P]),
@@ -255,6 +269,8 @@ def vit_config(dim: int, depth: int, patch: int, stride: int, img_h: int, img_w:
     _lib.lib().dvt_vit_struct_sizes(sizes)
     if list(sizes) != [C.sizeof(VitConfig), C.sizeof(VitBlockWeights), C.sizeof(VitWeights)]:
         raise _lib.DvtError("ViT struct layout mismatch between ctypes and C")
+    if int(_lib.lib().dvt_vit_taps_struct_size()) != C.sizeof(VitTaps):
+        raise _lib.DvtError("DvtVitTaps layout mismatch between ctypes and C")
     return cfg
 
 
@@ -548,6 +564,58 @@ class HipViT:
                                n_blocks, ws.data_ptr(), _lib.stream()), "dvt_vit_forward")
             b0 += nb
         return (out, cls) if return_cls else out
+
+    def forward_taps(self, img: torch.Tensor, blocks, norm: bool = True, return_prefix: bool = False, outs=None,
+                     max_batch: int = 128):
+        """Several layers of ONE forward (timm's forward_intermediates): img [B,3,H,W] fp32 (normalised) -> a list with one
+        [B, grid_h, grid_w, dim] fp32 map (NHWC) per entry of `blocks`, the patch tokens after that block.  `blocks`: 0-based
+        block indices, strictly ascending, each below depth, at most DVT_VIT_MAX_TAPS of them; the blocks up to the last one
+        run once.  norm=True: every map is final-norm'ed and holds the bits of forward_features(n_blocks=block + 1);
+        norm=False: the residual rows as they are.  return_prefix=True: a list of (map, prefix [B, n_prefix, dim]) tuples,
+        the prefix rows (cls, then the register tokens) of the same layer, normed or not like the map.  `outs`: one
+        preallocated contiguous map per tap (slices of a feature store).  Workspace, launch plan, memory cap and input
+        checks are forward_features'."""
+        _lib.require_cuda(img)
+        cfg = self.cfg
+        if img.dtype != torch.float32 or tuple(img.shape[1:]) != (3, cfg.img_h, cfg.img_w):
+            raise _lib.DvtError(f"expected fp32 [B,3,{cfg.img_h},{cfg.img_w}], got {tuple(img.shape)} {img.dtype}")
+        blocks = [int(b) for b in blocks]
+        if not 1 <= len(blocks) <= DVT_VIT_MAX_TAPS:
+            raise _lib.DvtError(f"forward_taps takes 1 to {DVT_VIT_MAX_TAPS} blocks, not {len(blocks)}")
+        if any(b < 0 or b >= cfg.depth for b in blocks) or any(b1 <= b0 for b0, b1 in zip(blocks, blocks[1:])):
+            raise _lib.DvtError(f"blocks must be strictly ascending indices below depth {cfg.depth}, not {blocks}")
+        img = img.contiguous()
+        B = img.shape[0]
+        shape = (B, cfg.grid_h, cfg.grid_w, cfg.dim)
+        if outs is None:
+            outs = [torch.empty(shape, device=self.device, dtype=torch.float32) for _ in blocks]
+        outs = list(outs)
+        if len(outs) != len(blocks):
+            raise _lib.DvtError(f"outs names {len(outs)} maps for {len(blocks)} blocks")
+        for o in outs:
+            _lib.require_cuda(o)
+            if o.dtype != torch.float32 or not o.is_contiguous() or tuple(o.shape) != shape:
+                raise _lib.DvtError("every out must be a contiguous [B, grid_h, grid_w, dim] fp32 tensor")
+        prefixes = ([torch.empty((B, cfg.n_prefix, cfg.dim), device=self.device, dtype=torch.float32) for _ in blocks]
+                    if return_prefix else None)
+        plan = self.launch_plan(B, max_batch)
+        ws = self._workspace(max(plan))
+        L = _lib.lib()
+        fwd = (L.dvt_vit_forward_f32x3_taps if self.x3 else L.dvt_vit_forward_f32_taps if self.dtype == "float32"
+               else L.dvt_vit_forward_taps)
+        taps = VitTaps()
+        taps.n_taps, taps.norm = len(blocks), int(bool(norm))
+        for t, b in enumerate(blocks):
+            taps.block[t] = b
+        b0 = 0
+        for nb in plan:
+            for t in range(len(blocks)):
+                taps.feat[t] = outs[t][b0:].data_ptr()
+                taps.prefix[t] = prefixes[t][b0:].data_ptr() if return_prefix else None
+            _lib.check(fwd(C.byref(cfg), C.byref(self.weights), img[b0:].data_ptr(), C.byref(taps), nb, ws.data_ptr(),
+                           _lib.stream()), "dvt_vit_forward_taps")
+            b0 += nb
+        return list(zip(outs, prefixes)) if return_prefix else outs
 
     def _memory_cap(self, max_batch: int) -> int:
         """`max_batch` bounded by what the device can hold NOW (the fp32 extractor's launches grew from 32 to 160

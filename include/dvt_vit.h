@@ -10,6 +10,8 @@
  * drop the cls token -> patch-token map written NHWC fp32 straight into the feature store
  * (the NCHW round trip of the reference, vit_wrapper.py:142 / main_img_denoising.py:323, is
  * omitted).
+ * The rest of that signature -- several `n` indices from one forward, return_prefix_tokens=True, norm=False (reference call
+ * sites online_denoiser.py:74-82, evaluation/eval_utils/misc.py:140-182) -- is dvt_vit_forward*_taps at the end of this file.
  *
  * Arithmetic: bf16 operands on v_mfma_f32_16x16x32_bf16 with fp32 accumulation; residual
  * stream, LayerNorm statistics, softmax and all epilogues in fp32 (== the reference's
@@ -250,6 +252,33 @@ int dvt_vit_forward_f32_cls(const DvtVitConfig* h_cfg, const DvtVitWeights* h_w,
                             int batch, int n_blocks, void* workspace, void* stream);
 int dvt_vit_forward_f32x3_cls(const DvtVitConfig* h_cfg, const DvtVitWeights* h_w, const float* img, float* feat, float* cls,
                               int batch, int n_blocks, void* workspace, void* stream);
+
+/* ---- several layers of ONE forward: timm's forward_intermediates(indices, return_prefix_tokens, norm) ----
+ * The three forwards with `feat` / `n_blocks` replaced by a tap list.  The blocks 0 .. block[n_taps - 1] run once; after block
+ * block[t] one row-local launch (the tap kernel) writes that block's residual rows -- the patch rows NHWC to feat[t], the
+ * prefix rows (cls, then the register tokens) to prefix[t] where it is not NULL.  norm != 0: the final LayerNorm (norm_w,
+ * norm_b, ln_eps) of every tapped row, through the device function of the final-norm launch: feat[t] then holds the bits
+ * dvt_vit_forward*(n_blocks = block[t] + 1) writes and prefix[t][:, 0] the bits of its _cls form.  norm == 0: the residual rows
+ * as they are.  Pad rows and phantom rows of the workspace are never read into an output; nothing is written behind an output.
+ * DVT_E_BADARG before any pointer is touched: n_taps outside 1 .. DVT_VIT_MAX_TAPS; a block index that is negative, not below
+ * depth or not above its predecessor (unsorted lists, duplicates); a NULL feat[t]; a prefix[t] with n_prefix == 0; and whatever
+ * the plain forward of the same arithmetic refuses (the bf16x3 one: SwiGLU configs, dim > 1024).  Workspace: that of the plain
+ * forward. */
+#define DVT_VIT_MAX_TAPS 16
+typedef struct DvtVitTaps {
+  int32_t n_taps;                   /* 1 .. DVT_VIT_MAX_TAPS */
+  int32_t norm;                     /* one flag for the whole call */
+  int32_t block[DVT_VIT_MAX_TAPS];  /* 0-based block indices, strictly ascending, each < depth */
+  float* feat[DVT_VIT_MAX_TAPS];    /* per tap: fp32 [batch, grid_h, grid_w, dim] */
+  float* prefix[DVT_VIT_MAX_TAPS];  /* per tap: fp32 [batch, n_prefix, dim], or NULL */
+} DvtVitTaps;
+int64_t dvt_vit_taps_struct_size(void); /* sizeof(DvtVitTaps), for the ctypes mirror */
+int dvt_vit_forward_taps(const DvtVitConfig* h_cfg, const DvtVitWeights* h_w, const float* img, const DvtVitTaps* h_taps,
+                         int batch, void* workspace, void* stream);
+int dvt_vit_forward_f32_taps(const DvtVitConfig* h_cfg, const DvtVitWeights* h_w, const float* img, const DvtVitTaps* h_taps,
+                             int batch, void* workspace, void* stream);
+int dvt_vit_forward_f32x3_taps(const DvtVitConfig* h_cfg, const DvtVitWeights* h_w, const float* img, const DvtVitTaps* h_taps,
+                               int batch, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }
