@@ -80,6 +80,22 @@ enum { EPI_BIAS = 0, EPI_QKV = 1, EPI_GELU = 2, EPI_RESID = 3, EPI_EMBED = 4, EP
 #define IS_GELU(E) ((E) == EPI_GELU || (E) == EPI_GELU_X3)
 #define IS_X3(E) ((E) == EPI_GELU_X3 || (E) == EPI_QKV_X3)
 
+// ---- tile order: blockIdx -> (m, n) tile, L2-aware (map_tile, map_tile_fast, map_tile_id, fd_make / fd_div) --------------
+#include "dvt_tile_map.h"
+
+// Streaming (nt) cache policy for epilogue traffic that is touched once per launch (g_vit_epi_policy; dvt_tune_set(1,
+// -200000 - mask)).  Policy only: no bit changes a result.
+enum { EPOL_RESID_LD = 1,   // the fp32 residual loads of the 256 x 256 residual epilogue
+       EPOL_RESID_ST = 2,   // ... its fp32 residual stores
+       EPOL_XB_ST = 4,      // ... its bf16 xb stores (the next GEMM reads them, but only after 1.1 GB more has passed)
+       EPOL_HID_ST = 8,     // the bf16 `out` stores of the bias / GELU / SwiGLU epilogues (hid)
+       EPOL_QKV_ST = 16,    // the qk and V^T stores of the qkv epilogue
+       EPOL_HID_SC1 = 32,   // the EPOL_HID_ST stores go out write-through (sc1: the line leaves the XCD's L2) instead of nt
+       EPOL_RESID_SC1 = 64, // ... the EPOL_RESID_ST stores
+       EPOL_ALL = 127,
+       // shipped (profiles/r07/README.md): the residual stream nt on all three of its paths, hid write-through
+       EPOL_DEFAULT = EPOL_RESID_LD | EPOL_RESID_ST | EPOL_XB_ST | EPOL_HID_ST | EPOL_HID_SC1 };
+
 struct GemmBArgs {
   const bf16_t* A;
   const bf16_t* W;
@@ -115,10 +131,12 @@ struct GemmBArgs {
   unsigned* dbg;      // timing builds of the 8p kernel (dvt_vit_debug_buffer): 24 u32 per wave group and workgroup
   int stagger_ticks;  // 8p: the first round of workgroups (one per CU) starts spread over this many 100-MHz ticks (0: together)
   int tpw;            // lab 8t: tiles per workgroup (generations of 256 workgroups walk tpw x 256 consecutive tiles)
-  // map_tile_fast: the tile order's divisors as multiply-shift pairs (fd_make), set by launch_gemm for the 256 x 256 kernels
-  unsigned fd_pg[2], fd_pb[2], fd_w[2], fd_hb[2];  // per_group = group * mt; per_block = mblock * group; width = group; hb = mblock
-  int tiles_full;     // N tiles in whole groups (nt / group * group): ids beyond group `tiles_full / group` take the slow path
-  int pf_next;        // 8p: late in its epilogue a workgroup touches the first pf_next (0..2) k-tiles' operand lines of tile
+  // map_tile_fast: the 8p kernel's tile order (XCD column sets, groups, blocks and their divisors as multiply-shift pairs;
+  // dvt_tile_map.h), set by launch_gemm for the 256 x 256 kernels.  ONLY gemm_bf16_kernel_8p reads it.  `group` / `mblock`
+  // above are what every other kernel (pp, 128 x 128, the lab kernels) walks, always as ONE column set: with xcols > 1
+  // ord.group is the column set's width (nt / xcols) and differs from `group` -- never mix the two in one kernel
+  TileOrder ord;
+  int pf_next;       // 8p: late in its epilogue a workgroup touches the first pf_next (0..2) k-tiles' operand lines of tile
                       // blockIdx + 256, the tile the next workgroup of its XCD walks (NextTilePf; dvt_tune_set(1, -570 - n))
   int abl;            // developer library, TIMING ONLY (dvt_tune_set(1, -560 - mask)): bit 0 = the epilogues do not park their
                       // accumulators in LDS (outputs are garbage): what the parking writes cost a tile
@@ -147,85 +165,6 @@ __device__ __forceinline__ void stage_tile(const bf16_t* __restrict__ X, int ld,
 
 __device__ __forceinline__ bf16x8 read_frag(const char* lds, int row, int chunk) {
   return *reinterpret_cast<const bf16x8*>(lds + row * 128 + ((chunk ^ (row & 7)) << 4));
-}
-
-// ---- L2-aware tile rasterisation ------------------------------------------------------------
-// Workgroups are dealt round-robin to the 8 XCDs (private 4 MiB L2 each), so (1) every XCD gets a
-// CONTIGUOUS run of the tile order, and (2) the order walks N in groups of `group` tiles whose W
-// slices (group * 128 * K * 2 B <= ~2.4 MB) stay L2-resident while all M panels stream past:
-//     order = (n_group, m_panel, n_in_group)
-// Plain "N fastest" re-streamed the whole W (4.7 MB for fc1/fc2 > L2) for every M panel:
-// ~3.6 GB of memory-side reads per fc1 launch instead of ~0.6 GB.
-struct TileMap {
-  int m, n;
-};
-__device__ __forceinline__ TileMap map_tile(int bid, int nwg, int mt, int nt, int group, int mblock = 1) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-  const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;  // bijective
-  const int per_group = group * mt;
-  int g = id / per_group;
-  const int full = nt / group;
-  int width = group;
-  if (g >= full) {  // last, narrower group
-    g = full;
-    width = nt - full * group;
-  }
-  const int rem = id - g * per_group;
-  TileMap t;
-  if (mblock <= 1) {
-    t.m = rem / width;
-    t.n = g * group + rem % width;
-  } else {
-    // (m block, n, m in block): the `mblock` tiles that share a W slab are ADJACENT in the order (they start
-    // together and walk k in lock-step), and an A panel is re-touched every `mblock` ids
-    const int per_block = mblock * width;
-    const int mb = rem / per_block, r2 = rem - mb * per_block;
-    const int left = mt - mb * mblock, hb = left < mblock ? left : mblock;
-    t.n = g * group + r2 / hb;
-    t.m = mb * mblock + r2 % hb;
-  }
-  return t;
-}
-
-// Unsigned division by a launch-invariant divisor d (1 <= d < 2^31) as multiply-high + shifts (Granlund-Montgomery, the
-// round-up form): l = ceil(log2 d), m = floor(2^32 (2^l - d) / d) + 1;  x / d = (t + ((x - t) >> 1)) >> (l - 1), t = hi32(m x),
-// exact for every x < 2^32 (l = 0, i.e. d = 1: m = 0, the formula degenerates -- handled).  The tile map of the 256 x 256 GEMM
-// divides wave-UNIFORM values by run-time divisors four to six times per workgroup; the scalar unit has no divide, so hipcc
-// expands each into ~30 VALU instructions with dependent v_rcp chains: 0.6 us from kernel entry to the first LDS-DMA issue,
-// 2.4 % of a K = 768 tile (profiles/r06/r06j_*).  With these it is a handful of s_mul_hi_u32 (tests/test_kernel_math_cpu.py
-// states the arithmetic; every GEMM test exercises it).
-inline void fd_make(unsigned d, unsigned (&fd)[2]) {
-  unsigned l = 0;
-  while ((1ull << l) < d) ++l;
-  fd[0] = d <= 1 ? 0u : (unsigned)((((1ull << l) - d) << 32) / d + 1);
-  fd[1] = l;
-}
-__device__ __forceinline__ unsigned fd_div(unsigned x, const unsigned (&fd)[2]) {
-  if (fd[1] == 0) return x;  // d = 1
-  const unsigned t = __umulhi(x, fd[0]);
-  return (t + ((x - t) >> 1)) >> (fd[1] - 1);
-}
-// map_tile with the regular divisors taken from the launch arguments; ids in the last, narrower N group and tiles of a short
-// last M block (rare) fall back to the generic divisions.  Same result as map_tile for every id.
-__device__ __forceinline__ TileMap map_tile_fast(const GemmBArgs& p, int bid, int nwg, int mt, int nt) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-  const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;  // bijective
-  const int group = p.group, mblock = p.mblock, per_group = group * mt;
-  if (id >= p.tiles_full * mt) return map_tile(bid, nwg, mt, nt, group, mblock);  // the narrower last group
-  const int g = (int)fd_div((unsigned)id, p.fd_pg), rem = id - g * per_group;
-  TileMap t;
-  if (mblock <= 1) {
-    t.m = (int)fd_div((unsigned)rem, p.fd_w);
-    t.n = g * group + rem - t.m * group;
-    return t;
-  }
-  const int per_block = mblock * group;
-  const int mb = (int)fd_div((unsigned)rem, p.fd_pb), r2 = rem - mb * per_block;
-  if (mt - mb * mblock < mblock) return map_tile(bid, nwg, mt, nt, group, mblock);  // a short last M block
-  const int nq = (int)fd_div((unsigned)r2, p.fd_hb);
-  t.n = g * group + nq;
-  t.m = mb * mblock + r2 - nq * mblock;
-  return t;
 }
 
 // GELU(x) = 0.5 x (1 + erf(x / sqrt 2)) (nn.GELU(), timm Mlp) = max(x, 0) - 0.5 |x| E(|x|), E = erfc(|x| / sqrt 2).
@@ -489,7 +428,7 @@ __device__ __forceinline__ void pf_retire(NextTilePf& f) {
 // NI: 16-row blocks per call (4: a wave's 64 x 64 block, 17 KB of LDS; 2: 32 x 64, 8.5 KB -- the persistent kernel's passes,
 // which leave half of the ring to the next tile's operands); `blk0` overrides the wave's LDS block (default: smem + wave *
 // EP_WAVE_BYTES)
-template <int EPI, int NI = 4>
+template <int EPI, int NI = 4, bool OUT_SC1 = false>
 __device__ __forceinline__ void gemm_epilogue_lds(const GemmBArgs& p, f32x4 (&acc)[NI][4], int m0,
                                                   int n0, int wm, int wn, int wave, int lane,
                                                   char* smem, char* blk0 = nullptr, NextTilePf* pf = nullptr) {
@@ -557,7 +496,13 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmBArgs& p, f32x4 (&ac
       }
       typedef unsigned u32x4v_t __attribute__((ext_vector_type(4)));
       const u32x4v_t hi = {pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
-      if (vst) *reinterpret_cast<u32x4v_t*>(vrow + (size_t)d * p.s_pad) = hi;
+      if (vst) {
+        u32x4v_t* vdst = reinterpret_cast<u32x4v_t*>(vrow + (size_t)d * p.s_pad);
+        if (EPI == EPI_QKV && p.nt_store)
+          __builtin_nontemporal_store(hi, vdst);
+        else
+          *vdst = hi;
+      }
       if constexpr (EPI == EPI_QKV_X3) {
         u32x4v_t lo;
 #pragma unroll
@@ -742,8 +687,14 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmBArgs& p, f32x4 (&ac
         continue;
       }
       u32x4_t* dst = reinterpret_cast<u32x4_t*>(p.out + (size_t)(mb + row) * ldo + nb + c8);
-      if (p.nt_store)
-        __builtin_nontemporal_store(val, dst);  // streamed output: do not displace the operand panels in L2
+      if constexpr (OUT_SC1) {
+        // write-through (sc1): the line does not stay in the XCD's L2 behind the store.  A buffer store based at the block,
+        // the row offset in the VGPR offset (see RS_ST)
+        typedef int i32x4s_t __attribute__((ext_vector_type(4)));
+        const __amdgpu_buffer_rsrc_t orc = __builtin_amdgcn_make_buffer_rsrc(p.out + (size_t)mb * ldo + nb, 0, 0x7fffffff, 0x00020000);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4s_t, val), orc, (row * ldo + c8) * 2, 0, 16);
+      } else if (p.nt_store)
+        __builtin_nontemporal_store(val, dst);  // streamed output: meant not to displace the operand panels in L2
       else
         *dst = val;
     }
@@ -860,6 +811,11 @@ __device__ __forceinline__ float row16_sum(float v) {
 // rounds of memory latency -- longer than the whole K = 768 k-loop.  Here all 16 float4 rows of a
 // 64-row half are requested up front (64 VGPRs; the k-loop's fragment registers are dead), and the
 // second half's requests go out as soon as the first half's accumulators are parked in LDS.
+// LD_AUX / ST_AUX: cache-policy bits (the intrinsics' aux argument: 0 default, 2 = nt, 16 = sc1, write-through) of the fp32
+// residual loads / stores; XB_NT: the bf16 xb stores carry the nt hint (launch_gemm picks the 8p kernel's instantiation from
+// g_vit_epi_policy; policy only, the values are the same).  The st_part stores (8 B per row and 64 columns, 0.3 % of the
+// epilogue's bytes) stay plain: as a second nt form they took the kernel from 230 to 234 VGPRs.
+template <int LD_AUX = 0, int ST_AUX = 0, bool XB_NT = false>
 __device__ __forceinline__ void gemm_epilogue_resid_sq(const GemmBArgs& p, f32x4 (&acc)[8][4], int mb,
                                                        int nb, int wave, int lane, char* smem, NextTilePf* pf = nullptr) {
   const int g = lane >> 4, lc = lane & 15, c4 = lc * 4;
@@ -871,11 +827,11 @@ __device__ __forceinline__ void gemm_epilogue_resid_sq(const GemmBArgs& p, f32x4
   const int loff = (g * p.N + c4) * 4;
   const int rstep = p.N * 16;  // bytes per 4 rows
   typedef int i32x4_t __attribute__((ext_vector_type(4)));
-#define RS_LD(it) __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xr, loff, (it) * rstep, 0))
+#define RS_LD(it) __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xr, loff, (it) * rstep, LD_AUX))
 // Stores put the row offset into the VGPR offset (soffset = literal 0): with an SGPR soffset the
 // compiler assumes there is no ">64-bit store data overwritten by the next VALU" hazard and emits
 // no wait state, but gfx950 showed exactly that corruption (lanes 12-15 of each 16, one dword).
-#define RS_ST(it, v) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4_t, v), xr, loff + (it) * rstep, 0, 0)
+#define RS_ST(it, v) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4_t, v), xr, loff + (it) * rstep, 0, ST_AUX)
 // LayerNorm producer side: bf16 copy of the new row piece (16 lanes x 8 B = 128 B per row) and the row's partial
 // (sum, sum of squares) over this wave's 64 columns: xor-reduce over the 16 lanes that hold the row
 #define RS_LN(it, o)                                                                                    \
@@ -884,7 +840,12 @@ __device__ __forceinline__ void gemm_epilogue_resid_sq(const GemmBArgs& p, f32x4
     uint2 pk_;                                                                                          \
     pk_.x = pack2((o).x, (o).y);                                                                        \
     pk_.y = pack2((o).z, (o).w);                                                                        \
-    *reinterpret_cast<uint2*>(p.xb + (size_t)row_ * p.N + nb + c4) = pk_;                               \
+    uint2* xbp_ = reinterpret_cast<uint2*>(p.xb + (size_t)row_ * p.N + nb + c4);                        \
+    if constexpr (XB_NT)                                                                                \
+      __builtin_nontemporal_store(__builtin_bit_cast(unsigned long long, pk_),                          \
+                                  reinterpret_cast<unsigned long long*>(xbp_));                         \
+    else                                                                                                \
+      *xbp_ = pk_;                                                                                      \
     float s1_ = ((o).x + (o).y) + ((o).z + (o).w);                                                      \
     float s2_ = ((o).x * (o).x + (o).y * (o).y) + ((o).z * (o).z + (o).w * (o).w);                      \
     s1_ = row16_sum(s1_);                                                                               \
@@ -1244,7 +1205,10 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 // STAMP (developer library only, schedule 12): the tile's anatomy in WALL time -- s_memrealtime (100 MHz, not the shader clock:
 // independent of DVFS) at kernel entry, at the first MFMA (prologue done), behind the k-loop, behind the last store's issue and
 // behind its retirement, + HW_ID / XCC_ID (which CU): 8 u32 per workgroup at p.dbg (tools/lab_gemm8p_anatomy.py).
-template <int EPI, bool STAMP = false, int AUX = 0>
+// KPOL: the cache policies that need an instruction form of their own (kpol_of; 0 = the kernel of rounds 5-6 unchanged): 1 nt
+// residual loads, 2 nt residual stores, 8 those stores sc1 instead, 4 nt xb stores (st_part stays plain, see gemm_epilogue_resid_sq), 16 sc1 `out` stores.  The nt
+// hint on the bf16 outputs stays the run-time GemmBArgs::nt_store.
+template <int EPI, bool STAMP = false, int AUX = 0, int KPOL = 0>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_bf16_kernel_8p(GemmBArgs p) {
   constexpr int P8_AUX_A = (AUX & 1) ? 2 : 0, P8_AUX_B = (AUX & 2) ? 2 : 0;  // nt on the A / W stream (lab schedules 14..16)
   __shared__ __attribute__((aligned(16))) char smem[8 * EP_WAVE_BYTES];  // 136 KB >= 8 half-tiles (128 KB)
@@ -1261,7 +1225,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
-  const TileMap tm = map_tile_fast(p, blockIdx.x, gridDim.x, p.M >> 8, p.N >> 8);
+  const TileMap tm = map_tile_fast(p.ord, blockIdx.x, gridDim.x, p.M >> 8, p.N >> 8);
+  // XCD-column order: a slot beyond this XCD's rectangle has no tile and the workgroup ends here (workgroup-uniform, before
+  // any barrier or memory access; the hardware drains the scalar loads first).  Written as the instruction, not as `return`:
+  // the second exit block costs the GELU and residual instantiations 4 VGPRs (236 / 234 against 232 / 230), the budget that
+  // lets a wave of the fit's streaming kernels share the SIMD
+  // INVARIANT: the compiler believes control goes on with m0 = -256, so NOTHING that touches memory through tm / m0 / n0 --
+  // the operand descriptors' LDS-DMA, the stagger loop excepted (it reads no tile) -- may move above this line.  The
+  // "memory" clobber forbids it to the compiler; keep it, and keep the map call and this exit ahead of every load when
+  // editing.  (Checked in the assembly of all instantiations: the exit precedes the first vector-memory / LDS instruction.)
+  if (tm.m < 0) asm volatile("s_endpgm" ::: "memory");
   const int m0 = tm.m * 256, n0 = tm.n * 256;
 
   f32x4 acc[8][4];
@@ -1313,17 +1286,18 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   if constexpr (STAMP) ts_[2] = __builtin_amdgcn_s_memrealtime();
   NextTilePf pf_{nullptr, p.pf_next, 0u, 0u};
   if (p.pf_next > 0 && (int)blockIdx.x + 256 < (int)gridDim.x) {
-    const TileMap tn = map_tile_fast(p, blockIdx.x + 256, gridDim.x, p.M >> 8, p.N >> 8);
-    pf_.src = tid < 256 ? p.A + (size_t)(tn.m * 256 + tid) * p.lda : p.W + (size_t)(tn.n * 256 + tid - 256) * p.ldw;
+    const TileMap tn = map_tile_fast(p.ord, blockIdx.x + 256, gridDim.x, p.M >> 8, p.N >> 8);
+    if (tn.m >= 0) pf_.src = tid < 256 ? p.A + (size_t)(tn.m * 256 + tid) * p.lda : p.W + (size_t)(tn.n * 256 + tid - 256) * p.ldw;
   }
   if constexpr (EPI == EPI_RESID) {
-    gemm_epilogue_resid_sq(p, acc, m0 + wm * 128, n0 + wn * 64, wave, lane, smem, &pf_);
+    gemm_epilogue_resid_sq<(KPOL & 1) ? 2 : 0, (KPOL & 2) ? ((KPOL & 8) ? 16 : 2) : 0, (KPOL & 4) != 0>(
+        p, acc, m0 + wm * 128, n0 + wn * 64, wave, lane, smem, &pf_);
   } else {
     f32x4(&lo)[4][4] = *reinterpret_cast<f32x4(*)[4][4]>(&acc[0]);
     f32x4(&hi)[4][4] = *reinterpret_cast<f32x4(*)[4][4]>(&acc[4]);
-    gemm_epilogue_lds<EPI>(p, lo, m0 + wm * 128, n0 + wn * 64, 0, 0, wave, lane, smem);
+    gemm_epilogue_lds<EPI, 4, (KPOL & 16) != 0>(p, lo, m0 + wm * 128, n0 + wn * 64, 0, 0, wave, lane, smem);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    gemm_epilogue_lds<EPI>(p, hi, m0 + wm * 128 + 64, n0 + wn * 64, 0, 0, wave, lane, smem, nullptr, &pf_);
+    gemm_epilogue_lds<EPI, 4, (KPOL & 16) != 0>(p, hi, m0 + wm * 128 + 64, n0 + wn * 64, 0, 0, wave, lane, smem, nullptr, &pf_);
   }
   pf_retire(pf_);
   if constexpr (STAMP) {
@@ -1356,32 +1330,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #ifdef DVT_LAB
 typedef const __attribute__((address_space(4))) GemmBArgs* kernarg_ptr_t;
 
-// tile of position `id` in the L2-aware order of map_tile (see there)
-__device__ __forceinline__ TileMap map_tile_id(int id, int mt, int nt, int group, int mblock) {
-  const int per_group = group * mt;
-  int g = id / per_group;
-  const int full = nt / group;
-  int width = group;
-  if (g >= full) {
-    g = full;
-    width = nt - full * group;
-  }
-  const int rem = id - g * per_group;
-  TileMap t;
-  if (mblock <= 1) {
-    t.m = rem / width;
-    t.n = g * group + rem % width;
-  } else {
-    const int per_block = mblock * width;
-    const int mbk = rem / per_block, r2 = rem - mbk * per_block;
-    const int left = mt - mbk * mblock, hb = left < mblock ? left : mblock;
-    t.n = g * group + r2 / hb;
-    t.m = mbk * mblock + r2 % hb;
-  }
-  return t;
-}
-
-
 #include "lab/dvt_vit_gemm4w.inc"
 #include "lab/dvt_vit_gemm8p_lab.inc"
 #include "lab/dvt_vit_lab.inc"
@@ -1389,15 +1337,28 @@ __device__ __forceinline__ TileMap map_tile_id(int id, int mt, int nt, int group
 
 // W bytes kept L2-resident per N-tile group.  4800 KiB = every N tile of a K = 768 GEMM in ONE group (qkv: 9
 // tiles, fc1: 12): each 393-KB A panel is then fetched once instead of once per group (measured: GEMMs 907 ->
-// 931 TF/s in the extractor; 9600 KiB the same, 1200 KiB 900).
+// 931 TF/s in the extractor; 9600 KiB the same, 1200 KiB 900).  Round 7, current kernel, 396 views: 1200 / 2400 / 4800 KiB
+// within +-1 % of each other on qkv and fc1 (profiles/r07/): the group budget no longer moves a launch.
 int g_vit_group_bytes = 4800 * 1024;
-// M panels per block of the tile order, 0 = auto: 4 when a group has >= 6 N tiles (qkv 9, fc1 12), else 1.
+// M panels per block of the tile order, 0 = auto (launch_gemm): on the swept launches (the four GEMMs of a bf16 ViT-B block,
+// >= 256 M panels) qkv 8, fc1 4, proj / fc2 2; elsewhere 4 when a group has >= 6 N tiles, else 1, as before.  Round 7 at 396 views (profiles/r07/r07k_*): qkv 4 -> 8 or 16 +6-8 %
+// (32: +1 %, 64: -5 %); fc1 flat from 2 to 16, 1 and 32 lose 2-7 %; proj 1 -> 2 or 4 +4-7 %, fc2 1 -> 2 +1 %, 8 and 16 lose.
+// Rounds 2-6 (4 / 1), measured with the round-2 kernel at 128 views:
 // PMC FETCH_SIZE per launch, 128 views (profiles/r02/pmc_vit/): qkv 1.57 -> 1.10 GB, fc1 1.65 -> 1.39 GB with
 // blocks of 4; the N = 768 GEMMs (3 N tiles) get WORSE with blocks (1.53 -> 1.68 GB) and keep n-fastest.
 // Time moves by +1 % only (919 -> 930 TF/s): the L2 misses are served by the memory-side cache.
 int g_vit_mblock = 0;
 // bf16 output stores with the non-temporal hint: measured no effect on time or FETCH_SIZE (kept as a knob)
 int g_vit_nt_store = 0;
+// XCD column sets of the 8p kernel's tile order (dvt_tile_map.h): 0 = auto (g_vit_xcols_bytes), 1 / 2 / 4 forced where it
+// divides the N tile count (dvt_tune_set(1, -70 - xcols)).
+int g_vit_xcols = 0;
+// auto: the smallest xcols that leaves one XCD at most this many bytes of W (dvt_tune_set(1, -100000 - KiB)); 0 = never
+// split (the order of rounds 2-6).  2400 KiB: fc1 at dim 768 (12 slabs of 384 KiB) runs as 2 column sets of 6.
+int g_vit_xcols_bytes = 2400 * 1024;
+// EPOL_* mask (dvt_tune_set(1, -200000 - mask)): streaming cache policy on the epilogues' once-touched traffic, 0 = none;
+// -200000 - 128 = auto
+int g_vit_epi_policy = -1;  // -1 = auto: EPOL_DEFAULT on the swept launches (launch_gemm), none elsewhere
 // LayerNorm folded into the qkv / fc1 GEMMs and the proj / fc2 residual epilogues (ln_fold)
 int g_vit_fuse_ln = 1;
 // schedule mask of attention_kernel_v2 (see its header).  15 = k-step-major S, accumulator-major P.V, no per-tile max tree,
@@ -1464,14 +1425,24 @@ int launch_gemm(const GemmBArgs& a0, hipStream_t s) {
     g = g > nt ? nt : g;
     while (g > 1 && nt % g) --g;
     a.group = g;
-    a.mblock = g_vit_mblock > 0 ? g_vit_mblock : (g >= 6 ? 4 : 1);
-    a.nt_store = g_vit_nt_store;
-    fd_make((unsigned)(a.group * (a.M / 256)), a.fd_pg);
-    fd_make((unsigned)(a.mblock * a.group), a.fd_pb);
-    fd_make((unsigned)a.group, a.fd_w);
-    fd_make((unsigned)(a.mblock > 0 ? a.mblock : 1), a.fd_hb);
-    a.tiles_full = nt / a.group * a.group;
+    // The round-7 defaults (M blocks, column sets, epilogue policy) hold for the launches they were measured on and for no
+    // other: the four GEMMs of a bf16 ViT-B block (qkv, fc1, proj, fc2 by epilogue AND shape) at >= 256 M panels, i.e. many
+    // rounds of 256 tiles (swept at 2005 and 2129 panels, profiles/r07/).  Everything else -- the patch embedding, SwiGLU,
+    // ViT-L / ViT-g, the fp32 extractor's bf16x3 launches (EPI_F32, EPI_*_X3, and its EPI_RESID at K = 3 dim), short launches
+    // -- keeps the order, the M blocks and the plain stores of rounds 2-6 unless a tune key says otherwise.
+    const bool swept = a.M / 256 >= 256 && ((EPI == EPI_QKV && a.N == 2304 && a.K == 768) || (EPI == EPI_GELU && a.N == 3072 && a.K == 768) ||
+                                            (EPI == EPI_RESID && a.N == 768 && (a.K == 768 || a.K == 3072)));
+    // M panels per block, auto (g_vit_mblock): rounds 2-6: 4 where a group has >= 6 N tiles, else 1.  Swept: qkv 8, fc1 4,
+    // proj / fc2 2
+    int mb_auto = g >= 6 ? 4 : 1;
+    if (swept) mb_auto = EPI == EPI_QKV ? 8 : (EPI == EPI_GELU ? 4 : 2);
+    a.mblock = g_vit_mblock > 0 ? g_vit_mblock : mb_auto;
+    // epilogue cache policy of this launch's outputs: a mask set by tune key holds for every launch but the X3 epilogues
+    // (the fp32 extractor's own), the default for the swept ones
+    const int epol = IS_X3(EPI) ? 0 : (g_vit_epi_policy >= 0 ? g_vit_epi_policy : (swept ? EPOL_DEFAULT : 0));
+    a.nt_store = (epol & (IS_QKV(EPI) ? EPOL_QKV_ST : EPOL_HID_ST)) ? 1 : g_vit_nt_store;
     const dim3 grid8((a.M / 256) * nt);
+    a.ord = tile_order_make(a.M / 256, nt, a.group, a.mblock, 1);  // (every kernel but the product 8p walks xcols = 1)
     if (g_vit_stagger_pct > 0 && grid8.x > 512) {  // (a launch of fewer than two rounds has nothing to de-synchronise)
       // (EPI_SWIGLU borrows the GELU epilogue's measured 10.5 us: its own has not been measured)
       const double epi_us = EPI == EPI_RESID ? 20.0 : ((IS_GELU(EPI) || EPI == EPI_SWIGLU) ? 10.5 : 5.6);
@@ -1563,7 +1534,47 @@ int launch_gemm(const GemmBArgs& a0, hipStream_t s) {
       return 0;
     }
 #endif
-    hipLaunchKernelGGL((gemm_bf16_kernel_8p<EPI>), grid8, dim3(512), 0, s, a);
+    // XCD column sets (dvt_tile_map.h): g_vit_xcols, or with 0 (auto) the smaller of {1, 2} that divides nt and leaves an
+    // XCD at most g_vit_xcols_bytes of W; 1 (the grouped order) where neither does.  Four column sets are never chosen
+    // here: at the one shape where they were measured (fc1, dim 768) they lose 2-3 % (profiles/r07/README.md).  Auto splits
+    // swept launches only (many rounds: the rectangles differ by up to `group` tiles per XCD, which a launch of about one
+    // round would pay as a whole extra round); a forced xcols holds for every launch but the X3 epilogues.
+    int xcols = 1;
+    if (!IS_X3(EPI)) {
+      if (g_vit_xcols > 0) xcols = g_vit_xcols;
+      else if (g_vit_xcols_bytes > 0 && swept)
+        for (int xc = 1; xc <= 2; xc *= 2)
+          if (nt % xc == 0 && (long long)(nt / xc) * 256 * a.K * 2 <= g_vit_xcols_bytes) {
+            xcols = xc;
+            break;
+          }
+    }
+    if (tile_order_xcols(nt, xcols) > 1) a.ord = tile_order_make(a.M / 256, nt, a.group, a.mblock, xcols);
+    const dim3 gridx(tile_order_grid(a.ord, a.M / 256, nt));
+    // policies that are an instruction form (gemm_bf16_kernel_8p's KPOL): the residual stream's -- one of its three bits, or
+    // all of them (dvt_vit_tune admits nothing else) -- and the write-through `out` stores of the bias / GELU epilogues
+#define LAUNCH_8P(KP) hipLaunchKernelGGL((gemm_bf16_kernel_8p<EPI, false, 0, KP>), gridx, dim3(512), 0, s, a)
+    bool launched = false;
+    if constexpr (EPI == EPI_RESID) {
+      const int sc1 = (epol & EPOL_RESID_SC1) ? 8 : 0;
+      launched = true;
+      switch ((epol & 7) | ((epol & EPOL_RESID_ST) ? sc1 : 0)) {
+        case 1: LAUNCH_8P(1); break;
+        case 2: LAUNCH_8P(2); break;
+        case 2 | 8: LAUNCH_8P(2 | 8); break;
+        case 4: LAUNCH_8P(4); break;
+        case 7: LAUNCH_8P(7); break;
+        case 7 | 8: LAUNCH_8P(7 | 8); break;
+        default: launched = false;
+      }
+    } else if constexpr (EPI == EPI_BIAS || EPI == EPI_GELU) {
+      if ((epol & EPOL_HID_ST) && (epol & EPOL_HID_SC1)) {
+        LAUNCH_8P(16);
+        launched = true;
+      }
+    }
+    if (!launched) LAUNCH_8P(0);
+#undef LAUNCH_8P
     DVT_CHECK_LAUNCH();
     return 0;
   }
@@ -2602,6 +2613,24 @@ int dvt_vit_tune(int v) {
   }
   if (v == -50 || v == -51) {  // non-temporal bf16 output stores off / on
     g_vit_nt_store = v == -51;
+    return 0;
+  }
+  if (v == -70 || v == -71 || v == -72 || v == -74) {  // 8p GEMM: XCD column sets of the tile order, -70 = auto
+    g_vit_xcols = -70 - v;
+    return 0;
+  }
+  if (v <= -100000 && v >= -100000 - 65536) {  // ... auto: W bytes per XCD (KiB) up to which a launch is not split further, 0 = never split
+    g_vit_xcols_bytes = (-100000 - v) * 1024;
+    return 0;
+  }
+  if (v == -200000 - 128) {  // ... auto (default)
+    g_vit_epi_policy = -1;
+    return 0;
+  }
+  if (v <= -200000 && v >= -200000 - EPOL_ALL) {  // streaming cache policy of the GEMM epilogues' once-touched traffic (EPOL_* mask)
+    const int rs = (-200000 - v) & 7;  // the residual stream's three bits: one of them or all (the instantiated kernels)
+    if (rs == 3 || rs == 5 || rs == 6) return DVT_E_BADARG;
+    g_vit_epi_policy = -200000 - v;
     return 0;
   }
   if (v <= -570 && v >= -572) {  // 8p GEMM: L2 prefetch of the next workgroup's first 0 / 1 / 2 k-tiles (NextTilePf; results do not depend on it)

@@ -268,6 +268,17 @@ int dvt_render_views(const float* img, int H, int W, const int32_t* boxes, float
  *             k-tiles, else 3) / 256x128 ping-pong (M a whole 256-tile, else 1) / 128x128 two-stage;
  *           values >= 16: KiB of W kept L2-resident per N-tile group of the tile rasterisation; -100 - b: b M panels per
  *             block of the tile order (0 = auto); -50 / -51: non-temporal bf16 output stores off / on;
+ *           -70 - x (x = 0, 1, 2, 4): XCD column sets of the 256x256 kernel's tile order -- each XCD keeps 1 / x of the N
+ *             tiles for the whole launch and 8 / x row sets split M (x is halved until it divides the N tile count);
+ *             0 = auto [default]: 2 on a measured launch (fc1 of ViT-B at >= 256 row panels) where that leaves an XCD at most
+ *             the threshold below of W and the whole W is more, else 1 = the grouped order;
+ *           -100000 - KiB: that threshold (default 2400; 0 = never split);
+ *           -200000 - mask (mask 0..127; 128 = auto [default]: mask 47 on the four GEMMs of a bf16 ViT-B block at >= 256 row
+ *             panels, where it was measured, none elsewhere): streaming cache policy on GEMM epilogue traffic that is touched once
+ *             -- 1 fp32 residual loads (nt), 2 fp32 residual stores (nt), 4 the bf16 copy of the residual rows (nt), 8 the
+ *             bf16 outputs of the bias / GELU / SwiGLU epilogues (nt), 16 the q | k and V^T stores (nt); 32: the stores of
+ *             bit 8 go out write-through (sc1) instead of nt (bias / GELU), 64: those of bit 2.  Of the residual bits 1, 2,
+ *             4 a mask holds one or all three (DVT_E_BADARG otherwise).  Results do not depend on any of these;
  *           -60 / -61: LayerNorm as its own kernels / folded into the qkv and fc1 GEMMs [default];
  *           -700 - pct (pct 0..400, default 0 = off): de-synchronised start of the 256x256 kernel's first round of workgroups,
  *             spread over pct % of the modelled tile time (round 5: no gain; results do not depend on it);
