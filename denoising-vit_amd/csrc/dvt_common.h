@@ -247,6 +247,14 @@ struct DvtProbeScope {
   }
 };
 int dvt_vit_tune(int gemm_variant);
+// ... which asks the units of the ViT extractor in this order -- the forward (dvt_vit.hip), the fp32 extractor
+// (dvt_vit_f32.hip), attention (dvt_vit_attn.hip), GEMM (dvt_vit_gemm.hip) -- and the first that knows v answers: 0 (taken),
+// DVT_E_BADARG (its own, refused) or VIT_TUNE_NOT_MINE, which never leaves dvt_vit_tune.  Every unit keeps its knobs to itself.
+constexpr int VIT_TUNE_NOT_MINE = 1;
+int vit_forward_tune(int v);
+int vit_f32_tune(int v);
+int vit_attn_tune(int v);
+int vit_gemm_tune(int v);
 int dvt_grid_tune(int lds_level_max);
 int dvt_adam_tune(int zero_all);
 int dvt_s2_tune(int mask);

@@ -1,5 +1,5 @@
-// Tile order of the bf16 GEMMs (dvt_vit.hip): blockIdx -> (m, n) tile.  Plain integer arithmetic, compiled for the device by
-// dvt_vit.hip and for the host by the stand-alone checker of tests/test_tile_map_xcols_cpu.py (which includes this file and
+// Tile order of the bf16 GEMMs (dvt_vit_gemm.hip): blockIdx -> (m, n) tile.  Plain integer arithmetic, compiled for the device by
+// dvt_vit_gemm.hip (through dvt_vit_dev.h) and for the host by the stand-alone checker of tests/test_tile_map_xcols_cpu.py (which includes this file and
 // nothing else), so what the test walks IS what the kernels run.
 #pragma once
 

@@ -25,7 +25,7 @@ int dvt_linear_fwd_big(const float* x, const float* w, const float* b, float* y,
 bool dvt_linear_big_ok(int m, int n, int k);
 int dvt_linear_fwd_big_epi(const float* x, const float* w, const float* b, float* y, int m, int n, int k, int epi,
                            const float* gamma, hipStream_t s);
-// bf16 GEMM kernels of dvt_vit.hip (fp32 accumulation), used by the bf16x3 mode below
+// bf16 GEMM kernels of dvt_vit_gemm.hip (fp32 accumulation) and the split-operand attention of dvt_vit_attn.hip, used by the bf16x3 mode below
 extern "C" int dvt_vit_gemm_f32out(const void* a, const void* w, const float* b, float* y, int m, int n, int k, void* stream);
 extern "C" int dvt_vit_gemm_residual(const void* a, const void* w, const float* b, const float* gamma, float* x, int m,
                                      int n, int k, void* stream);
@@ -396,8 +396,23 @@ extern "C" int64_t dvt_vit_workspace_bytes_f32(const DvtVitConfig* c, int batch)
   return carve_f32(c, batch, nullptr, nullptr);
 }
 
+namespace {
 int g_f32x3_exact_attention = 0;  // dvt_tune_set(1, -520 / -521): exact-fp32 attention inside the bf16x3 forward on / off
 int g_f32x3_unfused = 0;          // dvt_tune_set(1, -522 / -523): split kernels instead of the split epilogues on / off
+}  // namespace
+
+// This unit's share of dvt_tune_set(1, v) (dvt_vit_tune, dvt_vit.hip)
+int vit_f32_tune(int v) {
+  if (v == -520 || v == -521) {  // fp32 extractor, bf16x3 mode: exact-fp32 attention (-520) / bf16x3 attention (-521, default)
+    g_f32x3_exact_attention = v == -520;
+    return 0;
+  }
+  if (v == -522 || v == -523) {  // ... split kernels (-522) / split epilogues of the qkv and fc1 GEMMs (-523, default)
+    g_f32x3_unfused = v == -522;
+    return 0;
+  }
+  return VIT_TUNE_NOT_MINE;
+}
 
 namespace {
 struct VitWorkX3 {

@@ -1,4 +1,4 @@
-// dvt_vit_gemm4w.inc -- included by dvt_vit.hip inside its anonymous namespace (GemmBArgs, map_tile_id, pack2, EPI_*).
+// dvt_vit_gemm4w.inc -- included by dvt_vit_gemm.hip inside its anonymous namespace (GemmBArgs, map_tile_id, pack2, EPI_*).
 //
 // "4w": the 256 x 256 bf16 GEMM tile on FOUR waves -- one per SIMD, 128 x 128 outputs each (256 accumulator registers,
 // v_mfma_f32_32x32x16_bf16) -- as a PERSISTENT workgroup whose epilogue is DEFERRED: the finished tile leaves the

@@ -1,5 +1,5 @@
-// lab/dvt_vit_gemm8p_lab.inc -- the re-schedules and timing builds of the product's 8-phase GEMM (dvt_vit.hip,
-// gemm_bf16_kernel_8p): SM 1 "8m", 2 "8h", 3 cycle stamps, 6..9 ablations with WRONG results.  Included by dvt_vit.hip
+// lab/dvt_vit_gemm8p_lab.inc -- the re-schedules and timing builds of the product's 8-phase GEMM (dvt_vit_gemm.hip,
+// gemm_bf16_kernel_8p): SM 1 "8m", 2 "8h", 3 cycle stamps, 6..9 ablations with WRONG results.  Included by dvt_vit_gemm.hip
 // inside #ifdef DVT_LAB only; the product library has none of it.  SM = 0 here is the product schedule again (the body the
 // variants were derived from) and is never launched.  tools/lab_gemm8p_stamps.py, tools/lab_gemm8p.py drive it.
 template <int MODE, int SM>  // 0 steady state, 1 tile nk-2 (no issue in P3/P4), 2 tile nk-1 (no issue)

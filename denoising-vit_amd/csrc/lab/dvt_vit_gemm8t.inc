@@ -1,4 +1,4 @@
-// lab/dvt_vit_gemm8t.inc -- included by dvt_vit.hip (anonymous namespace, -DDVT_LAB only) right behind gemm_bf16_kernel_8p, whose
+// lab/dvt_vit_gemm8t.inc -- included by dvt_vit_gemm.hip (anonymous namespace, -DDVT_LAB only) right behind gemm_bf16_kernel_8p, whose
 // macros (P8B_TILE with its MODEs 3 / 4, P8_STAGE, P8_LANE_SETUP ...) it uses.  Developer library schedule 11.
 //
 // RESULT (round 6, profiles/r06/r06d_*, r06e_*): bit-identical to 8p; ALONE 2.4-4.5 % faster per GEMM at 398 views (qkv 1865 ->

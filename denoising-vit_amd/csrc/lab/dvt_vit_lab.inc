@@ -1,4 +1,4 @@
-// lab/dvt_vit_lab.inc -- SUPERSEDED kernels of the bf16 extractor, kept for A/B work only.  Included by dvt_vit.hip inside
+// lab/dvt_vit_lab.inc -- SUPERSEDED kernels of the bf16 extractor, kept for A/B work only.  Included by dvt_vit_gemm.hip inside
 // its anonymous namespace when the library is built with -DDVT_LAB (tools/build_lab.py -> libdvt_hip_lab.so); the product
 // library (libdvt_hip.so) does not contain them and dvt_tune_set rejects the values that would select them.
 //   gemm_bf16_kernel_256  256x128 lock-step three-stage ring (round 1;   dvt_tune_set(1, 2))
@@ -162,4 +162,145 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   gemm_epilogue_lds<EPI>(p, lo, m0 + wm * 128, n0 + wn * 64, 0, 0, wave, lane, smem);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // own reads of the block are complete
   gemm_epilogue_lds<EPI>(p, hi, m0 + wm * 128 + 64, n0 + wn * 64, 0, 0, wave, lane, smem);
+}
+
+// ---- host side of the developer build's GEMMs: its knobs, its share of launch_gemm<EPI> and of dvt_tune_set(1, v), the debug
+// buffer.  The product functions of dvt_vit_gemm.hip call these through one guarded line each.
+int g_vit_tpw = 0;           // 4w kernel: target tiles per workgroup, 0 = auto (dvt_tune_set(1, -200 - n))
+int g_vit_epi_abl = 0;       // dvt_tune_set(1, -560 - mask): GemmBArgs::abl
+int g_vit_abl4w = 0;         // dvt_tune_set(1, -300 - mask) while a 4w schedule (6..9) is selected: its ablation mask (EPI_BIAS, timing only)
+int g_vit_8p_build = 0;      // ... while schedule 5 is selected: timing build of the 8p kernel (3 stamps, 6..9 ablations; EPI_BIAS only)
+unsigned* g_vit_dbg = nullptr;  // dvt_vit_debug_buffer
+int g_vit_w4_grid = 0;       // dvt_tune_set(1, -600 - n): workgroups of the 4w kernel (0 = auto: a whole number per CU)
+
+// launch_gemm<EPI>, 256 x 256 branch, in front of the product's 8p launch: true = a lab kernel of the selected schedule took
+// the launch (*rc: its status); false = the product kernel is to run -- with a.abl set, as every lab launch carries it.
+// grid8 = one workgroup per tile, nt = N tiles; a.ord is the xcols = 1 order here.
+template <int EPI>
+bool lab_launch_gemm(GemmBArgs& a, hipStream_t s, const dim3 grid8, int nt, int* rc) {
+    a.abl = g_vit_epi_abl;
+    const int nk = a.K / GBK;
+    if constexpr (EPI == EPI_BIAS || EPI == EPI_GELU) {
+      if (g_vit_gemm_variant >= 6 && g_vit_gemm_variant <= 9 && a.K >= W4_MIN_K) {
+        // 4w: persistent runs of ~`tpw` tiles; the grid is a whole number of workgroups per CU
+        const int tiles = (a.M / 256) * nt;
+        const int tpw = g_vit_tpw > 0 ? g_vit_tpw : (nk <= 16 ? 3 : 1);
+        int per_cu = (tiles + 256 * tpw - 1) / (256 * tpw);
+        int nwg = 256 * (per_cu < 1 ? 1 : per_cu);
+        if (g_vit_w4_grid > 0) nwg = g_vit_w4_grid;
+        if (nwg > tiles) nwg = tiles;
+        const dim3 grid(nwg);
+        const int var = g_vit_gemm_variant - 6;  // 6: flush per tile, 7: deferred, 8: flush + fast GELU, 9: deferred + fast GELU
+        bool abl_done = false;
+        if constexpr (EPI == EPI_BIAS) {  // ablations (timing only, results are wrong): dvt_tune_set(1, -300 - mask)
+#define W4_ABL(n) if (g_vit_abl4w == n) { hipLaunchKernelGGL((gemm_bf16_kernel_4w<EPI, 1, n>), grid, dim3(256), 0, s, a); abl_done = true; }
+          W4_ABL(1) W4_ABL(2) W4_ABL(4) W4_ABL(8) W4_ABL(3) W4_ABL(5) W4_ABL(6) W4_ABL(7) W4_ABL(9) W4_ABL(14) W4_ABL(15)
+#undef W4_ABL
+        }
+        if (abl_done) {
+        } else if (var == 0) hipLaunchKernelGGL((gemm_bf16_kernel_4w<EPI, 0>), grid, dim3(256), 0, s, a);
+        else if (var == 1) hipLaunchKernelGGL((gemm_bf16_kernel_4w<EPI, 1>), grid, dim3(256), 0, s, a);
+        else if (var == 2) hipLaunchKernelGGL((gemm_bf16_kernel_4w<EPI, 2>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((gemm_bf16_kernel_4w<EPI, 3>), grid, dim3(256), 0, s, a);
+        *rc = (int)hipGetLastError();
+        return true;
+      }
+    }
+    bool lab_done = false;
+    if constexpr (EPI == EPI_BIAS) {  // the timing builds exist for the bias epilogue only (tools/lab_gemm8p_stamps.py)
+      if (g_vit_gemm_variant == 5 && g_vit_8p_build != 0) {
+        a.dbg = g_vit_dbg;
+        switch (g_vit_8p_build) {
+          case 3: hipLaunchKernelGGL((gemm_bf16_kernel_8p_lab<EPI, 3>), grid8, dim3(512), 0, s, a); break;
+          case 6: hipLaunchKernelGGL((gemm_bf16_kernel_8p_lab<EPI, 6>), grid8, dim3(512), 0, s, a); break;
+          case 7: hipLaunchKernelGGL((gemm_bf16_kernel_8p_lab<EPI, 7>), grid8, dim3(512), 0, s, a); break;
+          case 8: hipLaunchKernelGGL((gemm_bf16_kernel_8p_lab<EPI, 8>), grid8, dim3(512), 0, s, a); break;
+          default: hipLaunchKernelGGL((gemm_bf16_kernel_8p_lab<EPI, 9>), grid8, dim3(512), 0, s, a); break;
+        }
+        lab_done = true;
+      }
+    }
+    if constexpr (EPI == EPI_BIAS || EPI == EPI_QKV || EPI == EPI_GELU) {
+      if (!lab_done && g_vit_gemm_variant == 11 && nk >= 4 && grid8.x > 256) {  // "8t": persistent, overlapped tile boundary
+        // workgroups of g_vit_tpw tiles each (0: one workgroup per CU for the whole launch); a multiple of 8 (XCD affinity)
+        // generations of 256 workgroups: generation g walks tiles [g, g + 1) x tpw x 256 of the order in tpw lock-step rounds
+        const int tiles = (int)grid8.x;
+        a.tpw = g_vit_tpw > 0 ? g_vit_tpw : (tiles + 255) / 256;
+        const int nwg = (tiles + a.tpw * 256 - 1) / (a.tpw * 256) * 256;
+        hipLaunchKernelGGL((gemm_bf16_kernel_8t<EPI>), dim3(nwg), dim3(512), 0, s, a);
+        lab_done = true;
+      }
+    }
+    if (!lab_done && g_vit_gemm_variant >= 14 && g_vit_gemm_variant <= 16) {  // nt on the A (14) / W (15) / both (16) operand streams
+      if (g_vit_gemm_variant == 14) hipLaunchKernelGGL((gemm_bf16_kernel_8p<EPI, false, 1>), grid8, dim3(512), 0, s, a);
+      else if (g_vit_gemm_variant == 15) hipLaunchKernelGGL((gemm_bf16_kernel_8p<EPI, false, 2>), grid8, dim3(512), 0, s, a);
+      else hipLaunchKernelGGL((gemm_bf16_kernel_8p<EPI, false, 3>), grid8, dim3(512), 0, s, a);
+      lab_done = true;
+    }
+    if (!lab_done && g_vit_gemm_variant == 12) {  // the product kernel's tile anatomy (wall-clock stamps per workgroup)
+      a.dbg = g_vit_dbg;
+      hipLaunchKernelGGL((gemm_bf16_kernel_8p<EPI, true>), grid8, dim3(512), 0, s, a);
+      lab_done = true;
+    }
+    if (lab_done) {
+    } else if (g_vit_gemm_variant == 13) {  // round 5's walk of the ring (12 / 4 / 8 / 0 reads, run-time parity)
+      hipLaunchKernelGGL((gemm_bf16_kernel_8p_lab<EPI, 0>), grid8, dim3(512), 0, s, a);
+      lab_done = true;
+    } else if (g_vit_gemm_variant == 10) {
+      hipLaunchKernelGGL((gemm_bf16_kernel_8p_lab<EPI, 2>), grid8, dim3(512), 0, s, a);
+      lab_done = true;
+    } else if (g_vit_gemm_variant == 5) {
+      hipLaunchKernelGGL((gemm_bf16_kernel_8p_lab<EPI, 1>), grid8, dim3(512), 0, s, a);
+      lab_done = true;
+    } else if (g_vit_gemm_variant == 0) {
+      hipLaunchKernelGGL((gemm_bf16_kernel_sq<EPI>), grid8, dim3(512), 0, s, a);
+      lab_done = true;
+    }
+    if (lab_done) *rc = (int)hipGetLastError();
+    return lab_done;
+}
+
+// ... 256 x 128 branch, in front of the ping-pong kernel: schedule 2 = the lock-step kernel of the same tile
+template <int EPI>
+bool lab_launch_gemm_256(const GemmBArgs& a, hipStream_t s, int tiles, int* rc) {
+  if (g_vit_gemm_variant != 2) return false;
+  hipLaunchKernelGGL((gemm_bf16_kernel_256<EPI>), dim3(tiles), dim3(512), 0, s, a);
+  *rc = (int)hipGetLastError();
+  return true;
+}
+
+// vit_gemm_tune, where the product's chain has always asked the lab: behind its own negative keys, in front of -700 - pct,
+// -100 - b and the group budget (none of which overlaps a key here).  0 / DVT_E_BADARG / VIT_TUNE_NOT_MINE.
+int lab_gemm_tune(int v) {
+  if ((v <= -600 && v > -700) || (v < -1100 && v >= -1100 - 65536)) {  // -600 - n (n < 100) / -1100 - n: the 4w GEMM's grid forced to n workgroups (0 = auto)
+    g_vit_w4_grid = v > -700 ? -600 - v : -1100 - v;
+    return 0;
+  }
+  if (v <= -560 && v >= -563) {  // timing-only ablation of the GEMM epilogues (GemmBArgs::abl)
+    g_vit_epi_abl = -560 - v;
+    return 0;
+  }
+  if (v <= -300 && v > -399) {  // ablation mask of the selected 4w schedule / timing build of schedule 5; anything else: neither
+    const int n = -300 - v;
+    g_vit_abl4w = g_vit_8p_build = 0;
+    if (n == 0) return 0;
+    if (g_vit_gemm_variant >= 6 && g_vit_gemm_variant <= 9) g_vit_abl4w = n;
+    else if (g_vit_gemm_variant == 5 && (n == 3 || (n >= 6 && n <= 9))) g_vit_8p_build = n;
+    else return DVT_E_BADARG;
+    return 0;
+  }
+  if (v <= -200 && v > -300) {  // -200 - n: target tiles per workgroup of the 4w kernel, 0 = auto
+    g_vit_tpw = -200 - v > 64 ? 64 : -200 - v;
+    return 0;
+  }
+  if (v < 0 || v >= 16) return VIT_TUNE_NOT_MINE;  // (16 and up: the group budget in KiB, vit_gemm_tune)
+  g_vit_abl4w = g_vit_8p_build = 0;  // an ablation / timing build never survives a change of schedule
+  g_vit_gemm_variant = v;  // every schedule 0 .. 15 (see launch_gemm and lab_launch_gemm for the ones that name a kernel)
+  return 0;
+}
+
+// dvt_vit_debug_buffer
+bool lab_set_debug_buffer(void* dev_u32) {
+  g_vit_dbg = static_cast<unsigned*>(dev_u32);
+  return true;
 }

@@ -1,5 +1,5 @@
 // lab/dvt_vit_lab_attn.inc -- the round-2 attention loop ("v1": S -> softmax -> P.V strictly in sequence, tile max reduced
-// every tile), superseded by attention_kernel_v2 in round 3 (+10 %).  Included by dvt_vit.hip inside its anonymous namespace
+// every tile), superseded by attention_kernel_v2 in round 3 (+10 %).  Included by dvt_vit_attn.hip inside its anonymous namespace
 // under -DDVT_LAB only (dvt_tune_set(1, -501) of libdvt_hip_lab.so); shares KV_TILE / VT_LD / ATT_Q with the product kernel.
 __global__ __launch_bounds__(512) void attention_kernel(const bf16_t* __restrict__ qk,
                                                         const bf16_t* __restrict__ vt,
@@ -182,4 +182,84 @@ __global__ __launch_bounds__(512) void attention_kernel(const bf16_t* __restrict
     pk.y = pack2(o[mt][2] * inv, o[mt][3] * inv);
     *reinterpret_cast<uint2*>(orow + mt * 16 + 4 * g) = pk;
   }
+}
+
+// ---- host side of the developer build's attention: its knobs, its share of the two attention entry points and of
+// dvt_tune_set(1, v).  The product functions of dvt_vit_attn.hip call these through one guarded line each.
+int g_vit_attn_l2_mask = ATT_L2_VAR;  // dvt_tune_set(1, -540 - x): the product's mask (559 = 1 + 2 + 4 + 8 + 32 + 512) with the bits x toggled: 2 = P.V
+                                      // fragment by fragment, 512 = no group pattern for the K reads, 514 = both, 128 / 256 / 384 = ablations (idle
+                                      // waves compute / whole tail tile / both)
+int g_vit_attn_variant = 2;  // dvt_tune_set(1, -500 - v): 2 (default) = attention_kernel_v2, 1 = the round-2 kernel
+
+// dvt_vit_attention_log2q, in front of the product's launch: true = another build of the log2-domain kernel is selected and
+// took the launch (*rc: its status, DVT_E_BADARG for a mask no build exists for); false = the product's mask
+bool lab_launch_attention_l2(const void* qk, const void* vt, void* out, int heads, int s_pad, int n_valid, const dim3 grid,
+                             hipStream_t stream, int* rc) {
+  if (g_vit_attn_l2_mask == ATT_L2_VAR) return false;
+  {  // ablation builds / the other P.V order
+#define A2L_VAR(n)                                                                                                    \
+  if (g_vit_attn_l2_mask == (n)) {                                                                                    \
+    hipLaunchKernelGGL(attention_kernel_l2<(n)>, grid, dim3(512), 0, (hipStream_t)stream, (const bf16_t*)qk,          \
+                       (const bf16_t*)vt, (bf16_t*)out, heads, s_pad, n_valid);                                       \
+    *rc = (int)hipGetLastError();                                                                                     \
+    return true;                                                                                                      \
+  }
+    A2L_VAR(ATT_L2_VAR ^ 2) A2L_VAR(ATT_L2_VAR ^ 128) A2L_VAR(ATT_L2_VAR ^ 256) A2L_VAR(ATT_L2_VAR ^ 384) A2L_VAR(ATT_L2_VAR ^ 512)
+    A2L_VAR(ATT_L2_VAR ^ 514) A2L_VAR(ATT_L2_VAR ^ 1024) A2L_VAR(ATT_L2_VAR ^ 2048) A2L_VAR(ATT_L2_VAR ^ 4096) A2L_VAR(ATT_L2_VAR ^ 8192) A2L_VAR(ATT_L2_VAR ^ 16384) A2L_VAR(ATT_L2_VAR ^ 32768) A2L_VAR(ATT_L2_VAR ^ (32768 + 65536))
+#undef A2L_VAR
+    *rc = DVT_E_BADARG;
+    return true;
+  }
+}
+
+// whether the product's kernel and schedule mask are the selected ones (the forward pre-scales q only then)
+bool lab_attn_product_selected() { return g_vit_attn_variant == 2 && g_vit_attn_mask == 15; }
+
+// dvt_vit_attention, in front of the product's launch (attention_kernel_v2<15>): the round-2 kernel or another schedule mask
+bool lab_launch_attention(const void* qk, const void* vt, void* out, int heads, int s_pad, int n_valid, const dim3 grid,
+                          hipStream_t stream, int* rc) {
+  if (lab_attn_product_selected()) return false;
+  if (g_vit_attn_variant != 2) {
+    *rc = DVT_E_BADARG;
+    if (s_pad % ATT_Q) return true;  // (the round-2 loop has no query-block tail)
+    hipLaunchKernelGGL(attention_kernel, grid, dim3(512), 0, (hipStream_t)stream, (const bf16_t*)qk, (const bf16_t*)vt,
+                       (bf16_t*)out, heads, s_pad, n_valid);
+    *rc = (int)hipGetLastError();
+    return true;
+  }
+  bool done = false;
+#define A2_VAR(n)                                                                                                     \
+  if (g_vit_attn_mask == n) {                                                                                         \
+    hipLaunchKernelGGL(attention_kernel_v2<n>, grid, dim3(512), 0, (hipStream_t)stream, (const bf16_t*)qk,            \
+                       (const bf16_t*)vt, (bf16_t*)out, heads, s_pad, n_valid);                                       \
+    done = true;                                                                                                      \
+  }
+  A2_VAR(0) A2_VAR(1) A2_VAR(2) A2_VAR(4) A2_VAR(8) A2_VAR(16) A2_VAR(64) A2_VAR(3) A2_VAR(31) A2_VAR(79)
+#undef A2_VAR
+  *rc = done ? (int)hipGetLastError() : DVT_E_BADARG;
+  return true;
+}
+
+// vit_attn_tune, behind -530 / -531.  dvt_vit_tune asks attention BEFORE the GEMM, whose -700 - pct (0 .. 400) would
+// otherwise take -540 - 256 / 384 / 512 / 514.  The reverse case: -540 - 128 and -540 - 1024 ... -540 - 32768 lie in the 4w
+// GEMM's grid keys (-600 - n, -1100 - n), which the decoder has always asked first -- they set that grid, never reached
+// the list below, and are therefore not in it (attention_kernel_l2 builds of those masks exist, unselectable, as before).
+int lab_attn_tune(int v) {
+  if (v == -540 || v == -540 - 2 || v == -540 - 256 || v == -540 - 384 || v == -540 - 512 || v == -540 - 514 || v == -540 - 32768 - 65536) {
+    g_vit_attn_l2_mask = ATT_L2_VAR ^ (-540 - v);
+    return 0;
+  }
+  if (v <= -510 && v > -530) {
+    g_vit_attn_mask = -510 - v;
+    return 0;
+  }
+  if (v == -510 - 31 || v == -510 - 64 || v == -510 - 79) {
+    g_vit_attn_mask = -510 - v;
+    return 0;
+  }
+  if (v == -501 || v == -502) {
+    g_vit_attn_variant = -500 - v;
+    return 0;
+  }
+  return VIT_TUNE_NOT_MINE;
 }

@@ -24,6 +24,8 @@ HIP_SOURCES = [
     "dvt_fit.hip",
     "dvt_fit_fused.hip",
     "dvt_vit.hip",
+    "dvt_vit_gemm.hip",
+    "dvt_vit_attn.hip",
     "dvt_vit_f32.hip",
     "dvt_stage2.hip",
     "dvt_stage3.hip",
@@ -259,6 +261,8 @@ def register_signatures(extra: dict) -> None:
 def build(force: bool = False, verbose: bool = False, lab: bool = False) -> Path:
     """Compile every HIP source for gfx950 into csrc/libdvt_hip.so (hipcc cross-compiles without a GPU): one object per
     source, compiled in parallel, then one link.  Rebuilds only when a source/header is newer than the library.
+    The bf16 ViT extractor is three of those sources -- dvt_vit.hip (forward loop, small kernels), dvt_vit_gemm.hip (GEMMs; its
+    epilogues in dvt_vit_epilogue.h) and dvt_vit_attn.hip (attention) -- that share dvt_vit_dev.h and compile side by side.
     lab=True builds the DEVELOPER library csrc/libdvt_hip_lab.so with -DDVT_LAB (superseded schedules, experiments and
     timing builds of csrc/lab/); nothing in dvt_amd loads it (tools/build_lab.py, tools/lab_*.py, tests/test_gpu_lab.py)."""
     from concurrent.futures import ThreadPoolExecutor

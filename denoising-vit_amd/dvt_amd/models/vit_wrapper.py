@@ -2,7 +2,7 @@
 
 Same constructor arguments, properties (`n_output_dims`, `num_blocks`, `last_layer_index`,
 `patch_size`, `stride`, `transformation`) and `get_intermediate_layers` signature; the timm
-model behind it is replaced by the hand-written HIP forward (csrc/dvt_vit.hip).
+model behind it is replaced by the hand-written HIP forward (csrc/dvt_vit.hip and the GEMM / attention units it launches, csrc/dvt_vit_gemm.hip / dvt_vit_attn.hip).
 
 Differences forced by the environment (documented in DESIGN.md):
   * no network / no timm: `pretrained=True` cannot download.  Weights come from

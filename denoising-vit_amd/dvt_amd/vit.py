@@ -1,4 +1,4 @@
-"""Host side of the HIP ViT extractor (csrc/dvt_vit.hip, C ABI in include/dvt_vit.h).
+"""Host side of the HIP ViT extractor (csrc/dvt_vit.hip: forward loop; csrc/dvt_vit_gemm.hip, csrc/dvt_vit_attn.hip: its GEMMs and attention; C ABI in include/dvt_vit.h).
 
 Weights are accepted in the timm `VisionTransformer` state-dict layout the reference loads
 (`timm.create_model(model_identifier, pretrained=True, num_classes=0, dynamic_img_size=True)`,

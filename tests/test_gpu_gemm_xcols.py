@@ -1,4 +1,4 @@
-"""The XCD-column tile order and the epilogue cache policies of the 256 x 256 bf16 GEMM (csrc/dvt_vit.hip, dvt_tile_map.h)
+"""The XCD-column tile order and the epilogue cache policies of the 256 x 256 bf16 GEMM (csrc/dvt_vit_gemm.hip, dvt_tile_map.h)
 change WHERE and WHEN a tile runs and how its stores are cached, never a value: every output of every epilogue is compared
 bit for bit with the grouped order (xcols = 1) under the default policy, and the NaN-filled slack behind each output buffer
 must stay as it was (a tile mapped twice or outside M x N would show in one of the two).

@@ -16,7 +16,7 @@ from oracle import vit as ovit
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 ATTN_DEFAULT = 2   # dvt_tune_set(1, -500 - v): attention kernel of the bf16 extractor (1: round 2 [lab builds], 2: round 3)
-ATTN_MASK_DEFAULT = 15  # dvt_tune_set(1, -510 - mask): schedule mask of the round-3 kernel (csrc/dvt_vit.hip, attention_kernel_v2)
+ATTN_MASK_DEFAULT = 15  # dvt_tune_set(1, -510 - mask): schedule mask of the round-3 kernel (csrc/dvt_vit_attn.hip, attention_kernel_v2)
 # (kernel, mask).  The product library contains the shipped pair only; tests/test_gpu_lab.py runs the same checks on the
 # developer build's other kernels / masks (round 2; round 3 as first measured; the two-barrier ping-pong experiment)
 # "log2q" (round 6): the kernel dvt_vit_forward launches -- dvt_vit_attention_log2q, q PRE-SCALED by log2(e) / 8 (the qkv GEMM's
@@ -531,7 +531,7 @@ def test_vit_forward_f32x3_vs_oracle(L, dim, depth, img, stride, n_reg, knob):
 
 @pytest.mark.parametrize("depth,batch", [(3, 2), (12, 4)])
 def test_layernorm_folded_into_gemms(L, depth, batch):
-    """LayerNorm folded into the qkv / fc1 GEMMs and the proj / fc2 residual epilogues (dvt_vit.hip: ln_fold) against
+    """LayerNorm folded into the qkv / fc1 GEMMs and the proj / fc2 residual epilogues (dvt_vit_epilogue.h: ln_fold) against
     the LayerNorm kernels (dvt_tune_set(1, -60)) and the fp32 oracle, ViT-B/14 geometry, random LayerNorm affine
     parameters (so that gamma / beta folding is exercised), even batch = whole 256-row tiles."""
     from dvt_amd.vit import HipViT, random_state_dict

@@ -1,4 +1,4 @@
-"""Element-level parity of the bf16 extractor's GEMM epilogues (csrc/dvt_vit.hip) against fp64, one epilogue at a time.
+"""Element-level parity of the bf16 extractor's GEMM epilogues (csrc/dvt_vit_epilogue.h, launched by csrc/dvt_vit_gemm.hip) against fp64, one epilogue at a time.
 
 The whole-forward tests (tests/test_gpu_vit.py) hold every token to a cosine of 0.999; that cannot see a structural error in
 one epilogue (a V^T chunk stored into the wrong image moves an attention output by almost nothing).  Here every entry point

@@ -1,4 +1,4 @@
-"""CPU statements of arithmetic the bf16 extractor relies on: two pieces of its fc1 epilogue (csrc/dvt_vit.hip, gelu_erf /
+"""CPU statements of arithmetic the bf16 extractor relies on: two pieces of its fc1 epilogue (csrc/dvt_vit_epilogue.h, gelu_erf /
 gelu_erf_pair); the kernels themselves are held against the oracle by tests/test_gpu_vit.py.
 
 1. erf-GELU through Abramowitz-Stegun 7.1.28 with the powers of 1/sqrt(2) folded into the coefficients:
@@ -70,7 +70,7 @@ def test_relu_as_a_half_sum_is_exact_for_every_normal_fp32():
 
 
 def test_tile_map_multiply_shift_division():
-    """csrc/dvt_vit.hip fd_make / fd_div (round 6): the 256 x 256 GEMM's tile map divides by launch-invariant divisors with a
+    """csrc/dvt_tile_map.h fd_make / fd_div (round 6): the 256 x 256 GEMM's tile map divides by launch-invariant divisors with a
     multiply-high and two shifts (Granlund-Montgomery, round-up form) instead of hipcc's ~30-instruction VALU expansion of
     each run-time division.  The arithmetic, restated: l = ceil(log2 d), m = floor(2^32 (2^l - d) / d) + 1, t = hi32(m x),
     x // d = (t + ((x - t) >> 1)) >> (l - 1) -- exact for every 32-bit x; d = 1 is passed through."""
@@ -103,7 +103,7 @@ def test_tile_map_multiply_shift_division():
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# 3. The log2-domain attention loop (round 6; csrc/dvt_vit.hip, attention_v2_body with VAR bit 32 = dvt_vit_attention_log2q), stated
+# 3. The log2-domain attention loop (round 6; csrc/dvt_vit_attn.hip, attention_v2_body with VAR bit 32 = dvt_vit_attention_log2q), stated
 #    on the CPU for ONE wave = 16 queries of one (image, head), in the kernel's own fp32 / bf16 arithmetic:
 #      * q arrives as bf16(q * log2(e) / 8) -- the qkv GEMM's epilogue rounds ONCE, exactly as it rounds an unscaled q;
 #      * a tile's logits leave the matrix pipe as t = k . q' - m (the accumulation starts from C = -m, m = the running max in

@@ -8,7 +8,7 @@ Written from the published layout of timm 1.0.7's `vit_giant_patch14[_reg4]_dino
 A state dict whose fc1 has as many rows as fc2 has columns takes the GELU MLP of the S / B / L models instead.
 
 `round_bf16=True` is the comparator of the bf16 extractor's ARITHMETIC CLASS (the buffer list at the top of
-csrc/dvt_vit.hip): every matrix operand (weights, LayerNorm outputs, q | k | v, the softmax probabilities, the attention
+csrc/dvt_vit.hip and its GEMM / attention units): every matrix operand (weights, LayerNorm outputs, q | k | v, the softmax probabilities, the attention
 output, the hidden activations, the im2col patches) is rounded to bf16, everything else stays in `dtype`.
 
 `to_hf_dinov2_swiglu`: the independent second opinion, transformers' Dinov2Model / Dinov2WithRegistersModel with

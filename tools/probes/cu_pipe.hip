@@ -85,7 +85,7 @@ __global__ __launch_bounds__(512) void store_kernel(char* __restrict__ dst, size
 
 // ---- the GEMM's operand stream, alone.  One workgroup = one 256 x 256 tile of y = x W^T (x [M][K], W [N][K] bf16, row-major):
 // per k-tile (64 k) eight 8-KB pieces -- 4 of A (64 rows x 128 B at pitch 2K), 4 of W -- by LDS-DMA, D pieces in flight, nothing
-// else (no MFMA, no LDS reads, no stores).  Tile order = dvt_vit.hip's map_tile (every XCD a contiguous run of the order
+// else (no MFMA, no LDS reads, no stores).  Tile order = dvt_tile_map.h's map_tile (every XCD a contiguous run of the order
 // (n group, block of `mblock` M panels, n, m in block)).  Knobs:
 //   rot      0: every tile walks k = 0 .. nk-1 (the kernel today: the tiles that share an A panel / W slice ask for the same
 //               lines at the same time); 1: tile (m, n) starts at k-tile ((n * mblock + m % mblock) * nk) / (group * mblock)
