@@ -7,7 +7,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import attention_reference as AR
 from tests import test_gpu_vit as V
+from tests.test_gpu_attention_census import check_attention_census
 from tests.test_gpu_vit import DEV, GEMM_DEFAULT, _s
 
 pytestmark = pytest.mark.gpu
@@ -47,6 +49,13 @@ def test_lab_attention_vs_torch(L, batch, heads, s_pad, n_valid, attn_variant):
 @pytest.mark.parametrize("spike_tile,gain", V.SPIKES)
 def test_lab_attention_late_max_growth(L, attn_variant, spike_tile, gain):
     V.check_attention_late_max_growth(L, attn_variant, spike_tile, gain)
+
+
+@pytest.mark.parametrize("attn_variant", V.LAB_ATTN_CASES)
+@pytest.mark.parametrize("shape", AR.LAB_SHAPES, ids=AR.shape_id)
+def test_lab_attention_census(L, attn_variant, shape):
+    """The key census of tests/test_gpu_attention_census.py on the developer library's attention kernels and schedule masks."""
+    check_attention_census(L, attn_variant, shape)
 
 
 def test_lab_ablation_state_is_reset_by_a_schedule_change(L):
