@@ -19,8 +19,9 @@
 //   col    bf16 [batch*s_pad, k_patch]    im2col of the input image
 //   xb, st_part, stats                    bf16(x), partial row sums and (mean, rstd): the LayerNorm folded into the GEMMs
 //
-// This unit: configuration and workspace (VitWork / vit_carve), the forward loop (vit_forward_run and the three
-// dvt_vit_forward* entry points), dvt_vit_tune, and the small HBM-bound kernels around the GEMMs -- all launched by the product:
+// This unit: configuration and workspace (VitWork / vit_carve_geom), the forward (vit_forward_blocks: patch embedding + the
+// block loop vit_run_blocks, which the denoiser's forwards of dvt_denoiser.hip run over their own sequence; vit_forward_run and
+// the three dvt_vit_forward* entry points), dvt_vit_tune, and the small HBM-bound kernels around the GEMMs -- all launched by the product:
 //   im2col_pairs_kernel<14 / 16 / 8>, im2col_kernel   patch embedding's A operand (pairs: even geometry; else generic)
 //   ln_cast_stats_kernel<NV>, ln_stats_finalize_kernel  the folded LayerNorm's row statistics (default path)
 //   layernorm_kernel<false, NV>                       LayerNorm as a kernel (dvt_tune_set(1, -60), unfolded shapes)
@@ -249,18 +250,13 @@ __global__ __launch_bounds__(256) void tap_kernel(const float* __restrict__ x, c
 // LayerNorm folded into the qkv / fc1 GEMMs and the proj / fc2 residual epilogues (ln_fold)
 int g_vit_fuse_ln = 1;
 
-struct VitWork {
-  float* x;
-  bf16_t *xn, *qk, *vt, *hid, *col;
-  bf16_t* xb;       // bf16(x) for the LayerNorm-folded GEMMs
-  float2* st_part;  // [dim / 64][T] partial row sums from the residual epilogues
-  float2* stats;    // [T] (mean, rstd)
-};
+}  // namespace
 
-int64_t vit_carve(const DvtVitConfig* c, int batch, char* base, VitWork* w) {
+// (VitWork: dvt_vit_dev.h)
+int64_t vit_carve_geom(int s_pad, int dim, int mlp_dim, int k_patch, int batch, char* base, VitWork* w) {
   // rows: whole 256-row GEMM tiles -- an odd batch (s_pad = 1408 = 5.5 tiles) gets 128 phantom rows, computed and
   // never read, so that every batch takes the same kernels (results must not depend on how views are batched)
-  const int64_t T = ((int64_t)batch * c->s_pad + 255) / 256 * 256;
+  const int64_t T = ((int64_t)batch * s_pad + 255) / 256 * 256;
   int64_t o = 0;
   auto take = [&](int64_t bytes) {
     char* p = base ? base + o : nullptr;
@@ -268,21 +264,27 @@ int64_t vit_carve(const DvtVitConfig* c, int batch, char* base, VitWork* w) {
     return p;
   };
   VitWork t;
-  t.x = (float*)take(T * c->dim * 4);
-  t.xn = (bf16_t*)take(T * c->dim * 2);
+  t.x = (float*)take(T * dim * 4);
+  t.xn = (bf16_t*)take(T * dim * 2);
   // (+ 128 rows: where s_pad is not a multiple of 128 the attention kernel's last query block / key tile of the LAST image read
   // up to 127 rows past batch * s_pad -- never used: masked keys, unstored queries -- which T does not always cover)
-  t.qk = (bf16_t*)take((T + 128) * 2 * c->dim * 2);
+  t.qk = (bf16_t*)take((T + 128) * 2 * dim * 2);
   // (the phantom rows store no V^T (GemmBArgs::vt_rows): `batch` images are what is written and read; the spare image keeps
   // the layout of the workspace as it was)
-  t.vt = (bf16_t*)take(((int64_t)batch + 1) * c->s_pad * c->dim * 2);
-  t.hid = (bf16_t*)take(T * c->mlp_dim * 2);  // (SwiGLU: the half-width silu(gate) * value is all the fc1 GEMM writes)
-  t.col = (bf16_t*)take(T * c->k_patch * 2);
-  t.xb = (bf16_t*)take(T * c->dim * 2);
-  t.st_part = (float2*)take((int64_t)(c->dim / 64) * T * 8);
+  t.vt = (bf16_t*)take(((int64_t)batch + 1) * s_pad * dim * 2);
+  t.hid = (bf16_t*)take(T * mlp_dim * 2);  // (SwiGLU: the half-width silu(gate) * value is all the fc1 GEMM writes)
+  t.col = (bf16_t*)take(T * k_patch * 2);  // (the denoiser's sequences have no patch embedding: k_patch 0, no bytes)
+  t.xb = (bf16_t*)take(T * dim * 2);
+  t.st_part = (float2*)take((int64_t)(dim / 64) * T * 8);
   t.stats = (float2*)take(T * 8);
   if (w) *w = t;
   return o;
+}
+
+namespace {
+
+int64_t vit_carve(const DvtVitConfig* c, int batch, char* base, VitWork* w) {
+  return vit_carve_geom(c->s_pad, c->dim, c->mlp_dim, c->k_patch, batch, base, w);
 }
 
 // the final LayerNorm (fp32 out, prefix / pad rows dropped): the 4-slot instantiation up to dim 1024, 6 slots above (ViT-g)
@@ -495,28 +497,145 @@ int dvt_vit_launch_tap(const float* x, const DvtVitConfig* c, const float* norm_
   return 0;
 }
 
-extern "C" int64_t dvt_vit_taps_struct_size(void) { return (int64_t)sizeof(DvtVitTaps); }
+// What the denoiser's forwards (dvt_denoiser.hip) launch of this unit's kernels.
+int vit_check_cfg(const DvtVitConfig* c) { return check_vit_cfg(c); }
 
-// dvt_vit_forward (taps == NULL: n_blocks blocks, the final LayerNorm into feat) and dvt_vit_forward_taps (feat == NULL:
-// the blocks up to the last tap, one tap launch behind every tapped block) are the same launches in the same order.
-static int vit_forward_run(const DvtVitConfig* c, const DvtVitWeights* w, const float* img, float* feat,
-                           const DvtVitTaps* taps, int batch, int n_blocks, void* workspace, void* stream) {
-  int rc = check_vit_cfg(c);
-  if (rc) return rc;
-  if (!w || !img || (!feat && !taps) || !workspace || batch <= 0 || n_blocks < 0 || n_blocks > c->depth)
-    return DVT_E_BADARG;
-  hipStream_t s = (hipStream_t)stream;
-  VitWork k;
-  vit_carve(c, batch, (char*)workspace, &k);
-  const int T = (batch * c->s_pad + 255) / 256 * 256, D = c->dim;  // incl. phantom rows (vit_carve)
-  // algorithmic GEMM rows: the real tokens, not the rows padded to a multiple of 128
-  const double rows = (double)batch * c->n_tokens;
+int vit_launch_cls_norm(const float* x, const DvtVitConfig* c, const float* norm_w, const float* norm_b, float* cls, int batch,
+                        hipStream_t s) {
+  launch_final_norm(x, norm_w, norm_b, cls, batch, c->dim, c->ln_eps, c->s_pad, 1, 0, s);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
+int vit_launch_rows_out(const float* x, float* out, int batch, int s_pad, int n_valid, int dim, hipStream_t s) {
+  const int rows = batch * n_valid;
+  hipLaunchKernelGGL((tap_kernel<false, 4>), dim3(dvt_cdiv(rows, 4)), dim3(256), 0, s, x, (const float*)nullptr,
+                     (const float*)nullptr, out, (float*)nullptr, rows, dim, 0.f, s_pad, n_valid, 0);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int64_t dvt_vit_taps_struct_size(void) { return (int64_t)sizeof(DvtVitTaps); }
 
 #define DVT_TRY(x)         \
   do {                     \
     int rc__ = (x);        \
     if (rc__) return rc__; \
   } while (0)
+
+// LayerNorm folded into the GEMMs (ln_fold): needs the folded weights, the 8-phase kernel on every GEMM of the
+// block (whole 256-row / 256-column tiles) and is switched by dvt_vit_tune; otherwise the LayerNorm kernels run.
+bool vit_blocks_fold(const VitBlockGeom& g, const DvtVitBlockWeights* blocks, int n) {
+  const int T = (g.batch * g.s_pad + 255) / 256 * 256;
+  bool fuse_ln = g_vit_fuse_ln && vit_gemm_sq_schedule() && T % 256 == 0 && g.dim % 256 == 0 && g.mlp_dim % 256 == 0 && n > 0;
+  for (int l = 0; l < n; ++l) {
+    const DvtVitBlockWeights& bw = blocks[l];
+    fuse_ln = fuse_ln && bw.qkv_wf && bw.qkv_cs && bw.qkv_bf && bw.fc1_wf && bw.fc1_cs && bw.fc1_bf;
+  }
+  return fuse_ln;
+}
+
+// The block loop of every bf16 forward (the extractor's and the denoiser's): qkv GEMM -> attention -> proj GEMM (+ residual)
+// -> fc1 GEMM (GELU / SwiGLU) -> fc2 GEMM (+ residual), n times over the carved workspace.
+int vit_run_blocks(const VitBlockGeom& g, const DvtVitBlockWeights* blocks, int n_blocks, const VitWork& k, bool fuse_ln,
+                   int (*after_block)(void* ctx, int l), void* ctx, hipStream_t s) {
+  const int T = (g.batch * g.s_pad + 255) / 256 * 256, D = g.dim;  // incl. phantom rows (vit_carve_geom)
+  // algorithmic GEMM rows: the real tokens, not the rows padded to a multiple of 128
+  const double rows = (double)g.batch * g.n_valid;
+  const bool swiglu = g.swiglu != 0;
+  const int n_part = D / 64;
+  auto finalize_stats = [&]() { return launch_ln_stats_finalize(k.st_part, n_part, T, 1.0f / (float)D, g.eps, k.stats, s); };
+  const bool log2q = vit_attn_q_prescaled();
+  for (int l = 0; l < n_blocks; ++l) {
+    const DvtVitBlockWeights& bw = blocks[l];
+    if (!fuse_ln) DVT_TRY(dvt_vit_layernorm(k.x, bw.norm1_w, bw.norm1_b, k.xn, T, D, g.eps, s));
+    {
+      GemmBArgs a{};
+      a.A = fuse_ln ? k.xb : k.xn; a.W = (const bf16_t*)(fuse_ln ? bw.qkv_wf : bw.qkv_w); a.M = T; a.N = 3 * D; a.K = D;
+      a.bias = fuse_ln ? bw.qkv_bf : bw.qkv_b; a.out = k.qk; a.vt = k.vt;
+      if (fuse_ln) { a.ln_stats = k.stats; a.ln_cs = bw.qkv_cs; }
+      a.dim = D; a.heads = g.heads; a.s_pad = g.s_pad; a.n_tokens = g.n_valid; a.vt_rows = g.batch * g.s_pad;
+      a.work = 2.0 * rows * 3.0 * D * D;
+      a.q_scale = log2q ? ATT_Q_PRESCALE : 0.f;
+      DVT_TRY(launch_gemm<EPI_QKV>(a, s));
+    }
+    if (log2q) DVT_TRY(dvt_vit_attention_log2q(k.qk, k.vt, k.xn, g.batch, g.heads, g.s_pad, g.n_valid, s));
+    else DVT_TRY(dvt_vit_attention(k.qk, k.vt, k.xn, g.batch, g.heads, g.s_pad, g.n_valid, s));
+    {
+      GemmBArgs a{};
+      a.A = k.xn; a.W = (const bf16_t*)bw.proj_w; a.M = T; a.N = D; a.K = D;
+      a.bias = bw.proj_b; a.x = k.x; a.gamma = bw.ls1;
+      if (fuse_ln) { a.xb = k.xb; a.st_part = k.st_part; }
+      a.work = 2.0 * rows * D * D;
+      DVT_TRY(launch_gemm<EPI_RESID>(a, s));
+    }
+    if (fuse_ln) {
+      DVT_TRY(finalize_stats());
+    } else {
+      DVT_TRY(dvt_vit_layernorm(k.x, bw.norm2_w, bw.norm2_b, k.xn, T, D, g.eps, s));
+    }
+    {
+      GemmBArgs a{};
+      a.A = fuse_ln ? k.xb : k.xn; a.W = (const bf16_t*)(fuse_ln ? bw.fc1_wf : bw.fc1_w); a.M = T; a.N = g.mlp_dim; a.K = D;
+      a.bias = fuse_ln ? bw.fc1_bf : bw.fc1_b; a.out = k.hid;
+      if (fuse_ln) { a.ln_stats = k.stats; a.ln_cs = bw.fc1_cs; }
+      if (swiglu) {  // packed [2 mlp_dim, dim] weights -> the half-width silu(gate) * value
+        a.N = 2 * g.mlp_dim;
+        a.work = 2.0 * rows * 2.0 * g.mlp_dim * D;
+        DVT_TRY(launch_gemm<EPI_SWIGLU>(a, s));
+      } else {
+        a.work = 2.0 * rows * (double)g.mlp_dim * D;
+        DVT_TRY(launch_gemm<EPI_GELU>(a, s));
+      }
+    }
+    {
+      GemmBArgs a{};
+      a.A = k.hid; a.W = (const bf16_t*)bw.fc2_w; a.M = T; a.N = D; a.K = g.mlp_dim;
+      a.bias = bw.fc2_b; a.x = k.x; a.gamma = bw.ls2;
+      if (fuse_ln && l + 1 < n_blocks) { a.xb = k.xb; a.st_part = k.st_part; }
+      a.work = 2.0 * rows * (double)g.mlp_dim * D;
+      DVT_TRY(launch_gemm<EPI_RESID>(a, s));
+    }
+    if (fuse_ln && l + 1 < n_blocks) DVT_TRY(finalize_stats());
+    // (the fc2 epilogue of a tapped inner block has written xb and the partials too: x is stored before either, the same
+    // bits with or without them)
+    if (after_block) DVT_TRY(after_block(ctx, l));
+  }
+  return 0;
+}
+
+namespace {
+struct TapCtx {
+  const DvtVitConfig* c;
+  const DvtVitWeights* w;
+  const DvtVitTaps* taps;
+  const float* x;
+  int batch, tap;
+  hipStream_t s;
+};
+int tap_after_block(void* ctx, int l) {
+  TapCtx& t = *(TapCtx*)ctx;
+  if (t.tap < t.taps->n_taps && l == t.taps->block[t.tap]) {
+    DVT_TRY(dvt_vit_launch_tap(t.x, t.c, t.w->norm_w, t.w->norm_b, t.taps->feat[t.tap], t.taps->prefix[t.tap], t.batch,
+                               t.taps->norm, t.s));
+    ++t.tap;
+  }
+  return 0;
+}
+}  // namespace
+
+// The extractor up to the end of block n_blocks - 1: patch embedding, then the block loop (with `taps`, one tap launch behind
+// every tapped block).  What dvt_vit_forward, dvt_vit_forward_taps and dvt_vit_forward_denoised have in common.
+int vit_forward_blocks(const DvtVitConfig* c, const DvtVitWeights* w, const float* img, const DvtVitTaps* taps, int batch,
+                       int n_blocks, void* workspace, void* stream, VitWork* k_out) {
+  int rc = check_vit_cfg(c);
+  if (rc) return rc;
+  if (!w || !img || !workspace || batch <= 0 || n_blocks < 0 || n_blocks > c->depth) return DVT_E_BADARG;
+  hipStream_t s = (hipStream_t)stream;
+  VitWork k;
+  vit_carve(c, batch, (char*)workspace, &k);
+  if (k_out) *k_out = k;
+  const int T = (batch * c->s_pad + 255) / 256 * 256, D = c->dim;  // incl. phantom rows (vit_carve)
 
   // patch embedding: im2col -> GEMM with the (+bias, +pos_embed, cls) epilogue
   launch_im2col(c, img, k.col, T, batch * c->s_pad, s);
@@ -530,87 +649,33 @@ static int vit_forward_run(const DvtVitConfig* c, const DvtVitWeights* w, const 
     a.work = 2.0 * (double)batch * c->grid_h * c->grid_w * D * (3.0 * c->patch * c->patch);
     DVT_TRY(launch_gemm<EPI_EMBED>(a, s));
   }
-  // LayerNorm folded into the GEMMs (ln_fold): needs the folded weights, the 8-phase kernel on every GEMM of the
-  // block (whole 256-row / 256-column tiles) and is switched by dvt_vit_tune; otherwise the LayerNorm kernels run.
-  bool fuse_ln = g_vit_fuse_ln && vit_gemm_sq_schedule() && T % 256 == 0 && D % 256 == 0 && c->mlp_dim % 256 == 0 &&
-                 n_blocks > 0;
-  for (int l = 0; l < n_blocks; ++l) {
-    const DvtVitBlockWeights& bw = w->blocks[l];
-    fuse_ln = fuse_ln && bw.qkv_wf && bw.qkv_cs && bw.qkv_bf && bw.fc1_wf && bw.fc1_cs && bw.fc1_bf;
-  }
-  const bool swiglu = c->mlp_kind == DVT_VIT_MLP_SWIGLU;
-  const int n_part = D / 64;
-  auto finalize_stats = [&]() { return launch_ln_stats_finalize(k.st_part, n_part, T, 1.0f / (float)D, c->ln_eps, k.stats, s); };
+  VitBlockGeom g;
+  g.batch = batch; g.s_pad = c->s_pad; g.n_valid = c->n_tokens; g.heads = c->heads; g.dim = D; g.mlp_dim = c->mlp_dim;
+  g.swiglu = c->mlp_kind == DVT_VIT_MLP_SWIGLU; g.eps = c->ln_eps;
+  const bool fuse_ln = vit_blocks_fold(g, w->blocks, n_blocks);
   if (fuse_ln) {
     DVT_TRY(dvt_vit_ln_cast_stats(k.x, k.xb, k.stats, T, D, c->ln_eps, s));
   }
-  int tap = 0;
-  const bool log2q = vit_attn_q_prescaled();
-  for (int l = 0; l < n_blocks; ++l) {
-    const DvtVitBlockWeights& bw = w->blocks[l];
-    if (!fuse_ln) DVT_TRY(dvt_vit_layernorm(k.x, bw.norm1_w, bw.norm1_b, k.xn, T, D, c->ln_eps, s));
-    {
-      GemmBArgs a{};
-      a.A = fuse_ln ? k.xb : k.xn; a.W = (const bf16_t*)(fuse_ln ? bw.qkv_wf : bw.qkv_w); a.M = T; a.N = 3 * D; a.K = D;
-      a.bias = fuse_ln ? bw.qkv_bf : bw.qkv_b; a.out = k.qk; a.vt = k.vt;
-      if (fuse_ln) { a.ln_stats = k.stats; a.ln_cs = bw.qkv_cs; }
-      a.dim = D; a.heads = c->heads; a.s_pad = c->s_pad; a.n_tokens = c->n_tokens; a.vt_rows = batch * c->s_pad;
-      a.work = 2.0 * rows * 3.0 * D * D;
-      a.q_scale = log2q ? ATT_Q_PRESCALE : 0.f;
-      DVT_TRY(launch_gemm<EPI_QKV>(a, s));
-    }
-    if (log2q) DVT_TRY(dvt_vit_attention_log2q(k.qk, k.vt, k.xn, batch, c->heads, c->s_pad, c->n_tokens, s));
-    else DVT_TRY(dvt_vit_attention(k.qk, k.vt, k.xn, batch, c->heads, c->s_pad, c->n_tokens, s));
-    {
-      GemmBArgs a{};
-      a.A = k.xn; a.W = (const bf16_t*)bw.proj_w; a.M = T; a.N = D; a.K = D;
-      a.bias = bw.proj_b; a.x = k.x; a.gamma = bw.ls1;
-      if (fuse_ln) { a.xb = k.xb; a.st_part = k.st_part; }
-      a.work = 2.0 * rows * D * D;
-      DVT_TRY(launch_gemm<EPI_RESID>(a, s));
-    }
-    if (fuse_ln) {
-      DVT_TRY(finalize_stats());
-    } else {
-      DVT_TRY(dvt_vit_layernorm(k.x, bw.norm2_w, bw.norm2_b, k.xn, T, D, c->ln_eps, s));
-    }
-    {
-      GemmBArgs a{};
-      a.A = fuse_ln ? k.xb : k.xn; a.W = (const bf16_t*)(fuse_ln ? bw.fc1_wf : bw.fc1_w); a.M = T; a.N = c->mlp_dim; a.K = D;
-      a.bias = fuse_ln ? bw.fc1_bf : bw.fc1_b; a.out = k.hid;
-      if (fuse_ln) { a.ln_stats = k.stats; a.ln_cs = bw.fc1_cs; }
-      if (swiglu) {  // packed [2 mlp_dim, dim] weights -> the half-width silu(gate) * value
-        a.N = 2 * c->mlp_dim;
-        a.work = 2.0 * rows * 2.0 * c->mlp_dim * D;
-        DVT_TRY(launch_gemm<EPI_SWIGLU>(a, s));
-      } else {
-        a.work = 2.0 * rows * (double)c->mlp_dim * D;
-        DVT_TRY(launch_gemm<EPI_GELU>(a, s));
-      }
-    }
-    {
-      GemmBArgs a{};
-      a.A = k.hid; a.W = (const bf16_t*)bw.fc2_w; a.M = T; a.N = D; a.K = c->mlp_dim;
-      a.bias = bw.fc2_b; a.x = k.x; a.gamma = bw.ls2;
-      if (fuse_ln && l + 1 < n_blocks) { a.xb = k.xb; a.st_part = k.st_part; }
-      a.work = 2.0 * rows * (double)c->mlp_dim * D;
-      DVT_TRY(launch_gemm<EPI_RESID>(a, s));
-    }
-    if (fuse_ln && l + 1 < n_blocks) DVT_TRY(finalize_stats());
-    if (taps && tap < taps->n_taps && l == taps->block[tap]) {  // (the fc2 epilogue of a tapped inner block has written xb and the partials too: x is
-      // stored before either, the same bits with or without them)
-      DVT_TRY(dvt_vit_launch_tap(k.x, c, w->norm_w, w->norm_b, taps->feat[tap], taps->prefix[tap], batch, taps->norm, s));
-      ++tap;
-    }
-  }
-#undef DVT_TRY
+  TapCtx tc{c, w, taps, k.x, batch, 0, s};
+  return vit_run_blocks(g, w->blocks, n_blocks, k, fuse_ln, taps ? tap_after_block : nullptr, &tc, s);
+}
+
+// dvt_vit_forward (taps == NULL: n_blocks blocks, the final LayerNorm into feat) and dvt_vit_forward_taps (feat == NULL:
+// the blocks up to the last tap, one tap launch behind every tapped block) are the same launches in the same order.
+static int vit_forward_run(const DvtVitConfig* c, const DvtVitWeights* w, const float* img, float* feat,
+                           const DvtVitTaps* taps, int batch, int n_blocks, void* workspace, void* stream) {
+  if (!feat && !taps) return DVT_E_BADARG;
+  VitWork k;
+  DVT_TRY(vit_forward_blocks(c, w, img, taps, batch, n_blocks, workspace, stream, &k));
   if (taps) return 0;
   // final LayerNorm, drop cls/pad rows, NHWC fp32 straight into the feature store
   const int out_rows = batch * (c->n_tokens - c->n_prefix);
-  launch_final_norm(k.x, w->norm_w, w->norm_b, feat, out_rows, D, c->ln_eps, c->s_pad, c->n_tokens, c->n_prefix, s);
+  launch_final_norm(k.x, w->norm_w, w->norm_b, feat, out_rows, c->dim, c->ln_eps, c->s_pad, c->n_tokens, c->n_prefix,
+                    (hipStream_t)stream);
   DVT_CHECK_LAUNCH();
   return 0;
 }
+#undef DVT_TRY
 
 extern "C" int dvt_vit_forward(const DvtVitConfig* c, const DvtVitWeights* w, const float* img,
                                float* feat, int batch, int n_blocks, void* workspace,

@@ -3,6 +3,7 @@
 //   dvt_vit_gemm.hip  the bf16 GEMM family (its epilogues: dvt_vit_epilogue.h), launch_gemm<EPI>, the dvt_vit_gemm_* entry points
 //   dvt_vit_attn.hip  the attention kernels and the dvt_vit_attention* entry points
 //   dvt_vit.hip       im2col / LayerNorm / tap kernels, configuration, workspace and the forward loop
+//   dvt_denoiser.hip  the stage-2 denoiser's bf16 inference forwards: its entry kernel, then the same block loop
 // Here: the vector typedefs and the fp32 -> bf16 pack, the GEMM's argument block and epilogue / cache-policy enums, the tile
 // and query-block sizes the host code of several units computes grids and workspaces from, the bf16x3 scratch layout, and the
 // declarations of the host functions that cross units (bottom).  A __global__ kernel is launched only from the unit that
@@ -161,5 +162,39 @@ bool vit_gemm_sq_schedule();
 bool vit_attn_q_prescaled();
 // dvt_vit.hip: (mean, rstd) [rows] from the residual epilogues' partial sums part [n_part][rows] (ln_stats_finalize_kernel)
 int launch_ln_stats_finalize(const float2* part, int n_part, int rows, float inv_n, float eps, float2* stats, hipStream_t s);
+// dvt_vit.hip: the workspace of one forward and the block loop, shared with the denoiser's forwards (dvt_denoiser.hip)
+struct VitWork {
+  float* x;
+  bf16_t *xn, *qk, *vt, *hid, *col;
+  bf16_t* xb;       // bf16(x) for the LayerNorm-folded GEMMs
+  float2* st_part;  // [dim / 64][T] partial row sums from the residual epilogues
+  float2* stats;    // [T] (mean, rstd)
+};
+// what the block loop needs of a sequence: `batch` images of s_pad token rows each, the first n_valid of them tokens (the keys
+// the attention sees); T = batch * s_pad rounded up to whole 256-row tiles
+struct VitBlockGeom {
+  int batch, s_pad, n_valid, heads, dim, mlp_dim, swiglu;
+  float eps;
+};
+// ... the carve of `batch` images of s_pad rows (base == nullptr: the byte count alone; k_patch == 0: no im2col buffer)
+int64_t vit_carve_geom(int s_pad, int dim, int mlp_dim, int k_patch, int batch, char* base, VitWork* w);
+// ... whether n blocks at this geometry run with the LayerNorm folded into their GEMMs (the knob, the schedule, whole 256-wide
+// tiles, and the folded weights of every block)
+bool vit_blocks_fold(const VitBlockGeom& g, const DvtVitBlockWeights* blocks, int n);
+// ... blocks[0 .. n - 1] over the carved workspace k (x, and with fuse_ln also xb and stats, hold the sequence); after block l
+// after_block(ctx, l) runs where it is not NULL (the taps).  Launches only: the arguments are the caller's to check.
+int vit_run_blocks(const VitBlockGeom& g, const DvtVitBlockWeights* blocks, int n, const VitWork& k, bool fuse_ln,
+                   int (*after_block)(void* ctx, int l), void* ctx, hipStream_t s);
+// ... the extractor up to the end of its blocks (everything of dvt_vit_forward but the final LayerNorm); *k: its carve
+int vit_forward_blocks(const DvtVitConfig* c, const DvtVitWeights* w, const float* img, const DvtVitTaps* taps, int batch,
+                       int n_blocks, void* workspace, void* stream, VitWork* k);
+// ... the extractor's configuration check, and the final LayerNorm of the cls row of every image: cls [batch, dim] fp32 (the
+// launch of dvt_vit_forward_cls)
+int vit_check_cfg(const DvtVitConfig* c);
+int vit_launch_cls_norm(const float* x, const DvtVitConfig* c, const float* norm_w, const float* norm_b, float* cls, int batch,
+                        hipStream_t s);
+// ... the first n_valid rows of every image of x [batch * s_pad, dim] as they are -> out [batch, n_valid, dim] fp32: the tap
+// kernel without norm and without prefix rows (dim <= 1024)
+int vit_launch_rows_out(const float* x, float* out, int batch, int s_pad, int n_valid, int dim, hipStream_t s);
 // (the units' shares of dvt_tune_set(1, v) -- vit_forward_tune, vit_attn_tune, vit_gemm_tune and the fp32 extractor's
 // vit_f32_tune -- are declared next to dvt_vit_tune in dvt_common.h: dvt_vit_f32.hip does not include this header)

@@ -3,6 +3,7 @@ extractor) behind the reference's `dvt.models` API.  See DESIGN.md."""
 from . import _lib  # noqa: F401
 from . import vit  # noqa: F401  (registers the ViT entry points before the first library load)
 from . import s2  # noqa: F401  (stage-2 entry points)
+from . import denoiser_bf16  # noqa: F401  (the denoiser's bf16 inference entry points)
 from . import s3  # noqa: F401  (stage-3 entry points)
 from . import seg  # noqa: F401  (segmentation-evaluation entry points)
 from . import depth  # noqa: F401  (depth-evaluation entry points)

@@ -27,6 +27,7 @@ HIP_SOURCES = [
     "dvt_vit_gemm.hip",
     "dvt_vit_attn.hip",
     "dvt_vit_f32.hip",
+    "dvt_denoiser.hip",
     "dvt_stage2.hip",
     "dvt_stage3.hip",
     "dvt_seg.hip",

@@ -378,8 +378,14 @@ def get_args(argv=None):
     p.add_argument("--vit_checkpoint", help="timm-layout DINOv2 weights (timm cannot download here)")
     p.add_argument("--allow_random_vit", action="store_true", help="random ViT weights: tests and benchmarks only")
     p.add_argument("--dtype", default="bfloat16", choices=["float32", "bfloat16"], help="extractor arithmetic")
+    p.add_argument("--denoiser_dtype", default="float32", choices=["float32", "bfloat16"],
+                   help="arithmetic of the --load-denoiser-from denoiser's forward: float32 (exact, the default) or bfloat16 "
+                        "(the bf16 extractor's block kernels; needs --dtype bfloat16)")
     p.add_argument("--data-root", help="overrides data.train / data.val data_root")
     a = p.parse_args(argv)
+    if a.denoiser_dtype == "bfloat16" and a.dtype == "float32":
+        p.error("--denoiser_dtype bfloat16 with --dtype float32 is refused: a bf16 denoiser over an exact-fp32 extractor is "
+                "not a mode of the reference; pass --dtype bfloat16 or --denoiser_dtype float32 (nothing was written)")
     kind = config_kind(a.config)
     if kind != a.task:
         p.error(f"{a.config} is a {kind} config, not a {a.task} one: pass --task {kind}")
@@ -401,7 +407,7 @@ def build_backbone(args, device):
     den = None
     if args.load_denoiser_from:
         den = Denoiser(noise_map_height=37, noise_map_width=37, feat_dim=C, vit=None, num_blocks=args.num_blocks,
-                       device=device)
+                       device=device, inference_dtype=args.denoiser_dtype)
         sd = torch.load(args.load_denoiser_from, map_location="cpu", weights_only=False)
         den.load_state_dict(sd.get("denoiser", sd), strict=False)
     return S.ViTBackbone(vit._state_dict, vit.patch_size, device, dtype=args.dtype, denoiser=den), C
