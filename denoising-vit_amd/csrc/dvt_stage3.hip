@@ -330,12 +330,15 @@ struct S3Work {
   float *col, *wpad, *dwpad, *emb;
   float *d0, *d1, *d2, *dh, *dqkv, *dP, *acc, *wT, *rowdot;
   float *pos, *dpos, *ptmp;  // the run-grid position table, its gradient and the resample's [g0, gw, dim] intermediate
+  // gemm_mode 1 only: per block the qkv / proj / fc1 / fc2 weights as bf16, as stored [n, k] (the forward's B operand) and
+  // transposed [k, n] (the data gradient's), and one bf16 scratch for the A operand of the GEMM about to run
+  uint16_t *wb[DVT_VIT_MAX_DEPTH][4], *wtb[DVT_VIT_MAX_DEPTH][4], *abf;
 };
 
 // the table's grid differs from the run's: the step resamples pos_embed on its way in and its gradient on the way out
 bool resamples(const DvtVitConfig* c, int g0) { return g0 > 0 && (g0 != c->grid_h || g0 != c->grid_w); }
 
-int64_t carve(const DvtVitConfig* c, int batch, char* base, S3Work* w, int g0 = 0) {
+int64_t carve(const DvtVitConfig* c, int batch, char* base, S3Work* w, int g0 = 0, int mode = 0) {
   const int64_t R = (int64_t)batch * c->s_pad, C = c->dim, F = c->mlp_dim;
   const int64_t PP = (int64_t)batch * c->heads * c->s_pad * c->s_pad;
   int64_t o = 0;
@@ -386,6 +389,16 @@ int64_t carve(const DvtVitConfig* c, int batch, char* base, S3Work* w, int g0 = 
     t.dpos = take(n);
     t.ptmp = take((int64_t)g0 * c->grid_w * C);
   }
+  if (mode == 1) {  // behind everything else again: the fp32 mode's sizes and carving are what they were
+    auto take16 = [&](int64_t halves) { return reinterpret_cast<uint16_t*>(take((halves + 1) / 2)); };
+    const int64_t wn[4] = {3 * C * C, C * C, F * C, C * F};
+    for (int b = 0; b < c->depth; ++b)
+      for (int i = 0; i < 4; ++i) {
+        t.wb[b][i] = take16(wn[i]);
+        t.wtb[b][i] = take16(wn[i]);
+      }
+    t.abf = take16(R * (3 * C > F ? 3 * C : F));  // the widest A operand: a / dh [R, mlp_dim] or dqkv [R, 3 dim]
+  }
   if (w) *w = t;
   return o;
 }
@@ -416,15 +429,47 @@ int fork_to(hipStream_t s, hipStream_t sv) {
   return 0;
 }
 
+// ---- gemm_mode 1: the forward and the data gradient of a linear layer on the extractor's bf16 GEMM (dvt_vit_gemm.hip, EPI_F32:
+// bf16 operands, fp32 accumulation, fp32 output; m % 128 == n % 128 == k % 64 == 0, which check_cfg guarantees for every
+// layer of the block: R = batch s_pad with s_pad % 128 == 0, dim in {384, 768, 1024}, mlp_dim % 128 == 0).  The A operand is
+// rounded into `abf` right here; the weights were rounded at the top of run(). ----
+bool mp_shape_ok(int R, int n, int k) { return R > 0 && R % 128 == 0 && n % 128 == 0 && k % 64 == 0; }
+
+// y[R][n] = bf16(x)[R][k] . bf16(w)[n][k]^T + b
+int lin_fwd_mp(const float* x, const uint16_t* wb, const float* b, float* y, int R, int n, int k, uint16_t* abf, hipStream_t s) {
+  if (!mp_shape_ok(R, n, k)) return DVT_E_BADARG;
+  S2_TRY(dvt_s3_cast_bf16(x, abf, R, k, s));
+  return dvt_vit_gemm_f32out(abf, wb, b, y, R, n, k, s);
+}
+
+// dx[R][k] = bf16(dy)[R][n] . bf16(w^T)[k][n]^T;  dw[n][k] += dy^T . x and db[n] += colsum(dy) in exact fp32 from the UNROUNDED
+// dy and x, on lin_bwd's side stream beside the data gradient as in the fp32 mode
+int lin_bwd_mp(const float* dy, const float* x, const uint16_t* wtb, float* dx, float* dw, float* db, int R, int n, int k,
+               uint16_t* abf, hipStream_t s) {
+  if (!mp_shape_ok(R, k, n)) return DVT_E_BADARG;
+  hipStream_t sw = s;
+  const bool fork = g_s2_fork_wgrad && s2_side_stream(&sw);
+  if (!fork) sw = s;
+  S2_TRY(fork_to(s, sw));
+  S2_TRY(lin_bwd(dy, x, nullptr, nullptr, dw, db, R, n, k, sw));  // no dx: the weight and bias gradients alone, on sw
+  S2_TRY(dvt_s3_cast_bf16(dy, abf, R, n, s));
+  S2_TRY(dvt_vit_gemm_f32out(abf, wtb, nullptr, dx, R, k, n, s));
+  if (fork && (hipEventRecord(g_s2_ev_join, sw) != hipSuccess || hipStreamWaitEvent(s, g_s2_ev_join, 0) != hipSuccess))
+    return DVT_E_BADARG;
+  return 0;
+}
+
 int run(const DvtVitConfig* c, const float* params, float* grads, const float* img, const float* target, float* feat,
         int batch, int norm_batch, void* work, int64_t work_bytes, float* loss_out, hipStream_t s, int g0 = 0,
-        const float* wy = nullptr, const float* wx = nullptr) {
+        const float* wy = nullptr, const float* wx = nullptr, int mode = 0) {
   S2_TRY(check_cfg(c));
+  if (mode != 0 && mode != 1) return DVT_E_BADARG;
   const bool rs = resamples(c, g0);
   if (rs) S2_TRY(pos_check(wy, wx, g0, c->grid_h, c->grid_w, c->dim, c->pos_has_cls));
   if (!params || !grads || !img || !target || !loss_out || !work || batch < 1 || norm_batch < batch) return DVT_E_BADARG;
   S3Work w;
-  if (carve(c, batch, reinterpret_cast<char*>(work), &w, g0) > work_bytes) return DVT_E_BADARG;
+  if (carve(c, batch, reinterpret_cast<char*>(work), &w, g0, mode) > work_bytes) return DVT_E_BADARG;
+  if (mode == 1 && (!aligned16(params) || !aligned16(work))) return DVT_E_BADARG;  // (the casts move 16-byte pieces)
   int64_t po[8 + DVT_S3_TENSORS_PER_BLOCK * DVT_VIT_MAX_DEPTH];
   offsets(c, po, g0);
   const int C = c->dim, F = c->mlp_dim, T = c->n_tokens, Tp = c->s_pad, H = c->heads, NB = c->depth;
@@ -437,6 +482,24 @@ int run(const DvtVitConfig* c, const float* params, float* grads, const float* i
   auto P = [&](int b, int i) { return params + po[BLK0 + DVT_S3_TENSORS_PER_BLOCK * b + i]; };
   auto G = [&](int b, int i) { return grads + po[BLK0 + DVT_S3_TENSORS_PER_BLOCK * b + i]; };
   const int64_t normw = po[BLK0 + DVT_S3_TENSORS_PER_BLOCK * NB], normb = po[BLK0 + DVT_S3_TENSORS_PER_BLOCK * NB + 1];
+  const bool mp = mode == 1;
+  enum { WQKV = 0, WPROJ, WFC1, WFC2 };
+  // the four linear layers of a block in either mode (i: the layer's weight among the block's tensors, j: among its bf16 copies)
+  auto fwd = [&](int b, int i, int j, const float* x, float* y, int n, int k) {
+    return mp ? lin_fwd_mp(x, w.wb[b][j], P(b, i + 1), y, R, n, k, w.abf, s) : lin_fwd(x, P(b, i), P(b, i + 1), y, R, n, k, s);
+  };
+  auto bwd = [&](int b, int i, int j, const float* dy, const float* x, float* dx, int n, int k) {
+    return mp ? lin_bwd_mp(dy, x, w.wtb[b][j], dx, G(b, i), G(b, i + 1), R, n, k, w.abf, s)
+              : lin_bwd(dy, x, P(b, i), dx, G(b, i), G(b, i + 1), R, n, k, s, w.wT);
+  };
+  if (mp) {  // the weights of this call, rounded once: `params` changes between steps, and a slice is a step's unit
+    const int wi[4] = {QKVW, PROJW, FC1W, FC2W}, wn[4] = {3 * C, C, F, C}, wk[4] = {C, C, C, F};
+    for (int b = 0; b < NB; ++b)
+      for (int j = 0; j < 4; ++j) {
+        S2_TRY(dvt_s3_cast_bf16(P(b, wi[j]), w.wb[b][j], wn[j], wk[j], s));
+        S2_TRY(dvt_s3_cast_bf16_t(P(b, wi[j]), w.wtb[b][j], wn[j], wk[j], s));
+      }
+  }
 
   // ---- forward: patch embedding, token assembly, block 0's norm1 ----
   {
@@ -456,21 +519,21 @@ int run(const DvtVitConfig* c, const float* params, float* grads, const float* i
   // ---- the blocks ----
   for (int b = 0; b < NB; ++b) {
     const S3Block& k = w.blk[b];
-    S2_TRY(lin_fwd(k.xn1, P(b, QKVW), P(b, QKVB), k.qkv, R, 3 * C, C, s));
+    S2_TRY(fwd(b, QKVW, WQKV, k.xn1, k.qkv, 3 * C, C));
     hipLaunchKernelGGL(s2_attn_rows_kernel<0>, dim3((Tp / AR_Q) * H * batch), dim3(256), 0, s, (const float*)k.qkv, 3 * C,
                        (const float*)(k.qkv + C), 3 * C, (const float*)nullptr, (const float*)nullptr, k.P, H, T, Tp, scale);
     DVT_CHECK_LAUNCH();
     DvtGemmEx g = attn_gemm(ad, 1, k.P, Tp, ps0, ps1, k.qkv + 2 * C, 3 * C, qs0, qs1, k.ao, C, os0, os1, Tp, 64, Tp);
     S2_TRY(dvt_gemm_f32_ex(&g, s));
-    S2_TRY(lin_fwd(k.ao, P(b, PROJW), P(b, PROJB), k.f1, R, C, C, s));
+    S2_TRY(fwd(b, PROJW, WPROJ, k.ao, k.f1, C, C));
     S2_TRY(ls_add_ln(C, k.xin, k.f1, P(b, LS1), k.x1, P(b, N2W), P(b, N2B), k.xn2, k.mean2, k.rstd2, T, Tp, R, c->ln_eps, s));
-    S2_TRY(lin_fwd(k.xn2, P(b, FC1W), P(b, FC1B), k.h, R, F, C, s));
+    S2_TRY(fwd(b, FC1W, WFC1, k.xn2, k.h, F, C));
     {
       const int64_t n4 = (int64_t)R * F / 4;
       hipLaunchKernelGGL(s2_gelu_kernel, dim3(dvt_cdiv(n4, 256)), dim3(256), 0, s, (const float4*)k.h, (float4*)k.a, n4);
       DVT_CHECK_LAUNCH();
     }
-    S2_TRY(lin_fwd(k.a, P(b, FC2W), P(b, FC2B), k.f2, R, C, F, s));
+    S2_TRY(fwd(b, FC2W, WFC2, k.a, k.f2, C, F));
     if (b + 1 < NB) {
       const S3Block& n = w.blk[b + 1];
       S2_TRY(ls_add_ln(C, k.x1, k.f2, P(b, LS2), n.xin, P(b + 1, N1W), P(b + 1, N1B), n.xn1, n.mean1, n.rstd1, T, Tp, R,
@@ -491,17 +554,17 @@ int run(const DvtVitConfig* c, const float* params, float* grads, const float* i
     const S3Block& k = w.blk[b];
     // mlp: out = x1 + ls2 (.) fc2(gelu(fc1(norm2(x1))))
     S2_TRY(ls_bwd(C, w.d0, k.f2, P(b, LS2), w.d1, G(b, LS2), R, s));  // d1 = d f2
-    S2_TRY(lin_bwd(w.d1, k.a, P(b, FC2W), w.dh, G(b, FC2W), G(b, FC2B), R, C, F, s, w.wT));
+    S2_TRY(bwd(b, FC2W, WFC2, w.d1, k.a, w.dh, C, F));
     {
       const int64_t n4 = (int64_t)R * F / 4;
       hipLaunchKernelGGL(s2_gelu_bwd_kernel, dim3(dvt_cdiv(n4, 256)), dim3(256), 0, s, (const float4*)k.h, (float4*)w.dh, n4);
       DVT_CHECK_LAUNCH();
     }
-    S2_TRY(lin_bwd(w.dh, k.xn2, P(b, FC1W), w.d2, G(b, FC1W), G(b, FC1B), R, F, C, s, w.wT));
+    S2_TRY(bwd(b, FC1W, WFC1, w.dh, k.xn2, w.d2, F, C));
     S2_TRY(ln_bwd(C, w.d2, k.x1, k.mean2, k.rstd2, P(b, N2W), w.d0, w.d1, G(b, N2W), G(b, N2B), R, s));  // d1 = d x1
     // attention: x1 = xin + ls1 (.) proj(attn(norm1(xin)))
     S2_TRY(ls_bwd(C, w.d1, k.f1, P(b, LS1), w.d0, G(b, LS1), R, s));  // d0 = d f1
-    S2_TRY(lin_bwd(w.d0, k.ao, P(b, PROJW), w.d2, G(b, PROJW), G(b, PROJB), R, C, C, s, w.wT));  // d2 = d ao
+    S2_TRY(bwd(b, PROJW, WPROJ, w.d0, k.ao, w.d2, C, C));  // d2 = d ao
     {
       // as the stage-2 step: dV = P^T dao on the side stream beside the dS chain, dS = scale P (.) (dao v^T - rowsum) in the
       // attention-row kernel, then dq = dS k here and dk = dS^T q on the side stream; joined before lin_bwd reads dqkv
@@ -524,7 +587,7 @@ int run(const DvtVitConfig* c, const float* params, float* grads, const float* i
       if (fork && (hipEventRecord(g_s2_ev_join, sv) != hipSuccess || hipStreamWaitEvent(s, g_s2_ev_join, 0) != hipSuccess))
         return DVT_E_BADARG;
     }
-    S2_TRY(lin_bwd(w.dqkv, k.xn1, P(b, QKVW), w.d2, G(b, QKVW), G(b, QKVB), R, 3 * C, C, s, w.wT));
+    S2_TRY(bwd(b, QKVW, WQKV, w.dqkv, k.xn1, w.d2, 3 * C, C));
     S2_TRY(ln_bwd(C, w.d2, k.xin, k.mean1, k.rstd1, P(b, N1W), w.d1, w.d0, G(b, N1W), G(b, N1B), R, s));  // d0 = d xin
   }
   // ---- token assembly and patch embedding ----
@@ -604,6 +667,20 @@ extern "C" int dvt_s3_param_offsets_pos(const DvtVitConfig* cfg, int g0, int64_t
 extern "C" int64_t dvt_s3_workspace_bytes_pos(const DvtVitConfig* cfg, int batch, int g0) {
   if (check_cfg(cfg) != 0 || batch < 1 || g0 < 1) return -1;
   return carve(cfg, batch, nullptr, nullptr, g0);
+}
+
+extern "C" int64_t dvt_s3_workspace_bytes_mp(const DvtVitConfig* cfg, int batch, int g0, int gemm_mode) {
+  if (check_cfg(cfg) != 0 || batch < 1 || g0 < 0 || (gemm_mode != 0 && gemm_mode != 1)) return -1;
+  return carve(cfg, batch, nullptr, nullptr, g0, gemm_mode);
+}
+
+extern "C" int dvt_s3_train_slice_pos_mp(const DvtVitConfig* cfg, int g0, const float* wy, const float* wx, int gemm_mode,
+                                         const float* params, float* grads, const float* img, const float* target,
+                                         float* feat_out, int batch, int norm_batch, void* work, int64_t work_bytes,
+                                         float* loss_out, void* stream) {
+  if (g0 < 0 || (gemm_mode != 0 && gemm_mode != 1)) return DVT_E_BADARG;
+  return run(cfg, params, grads, img, target, feat_out, batch, norm_batch, work, work_bytes, loss_out, (hipStream_t)stream, g0,
+             wy, wx, gemm_mode);
 }
 
 extern "C" int dvt_s3_train_slice_pos(const DvtVitConfig* cfg, int g0, const float* wy, const float* wx, const float* params,

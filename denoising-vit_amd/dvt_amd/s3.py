@@ -11,6 +11,10 @@ A checkpoint whose position table has another grid than the run (`pos_grid`): `p
 all four arenas; every step resamples it to the run's grid (dvt_pos_resample_fwd, what timm's dynamic_img_size does in every
 forward) and carries the gradient back through the transpose (dvt_pos_resample_bwd, what autograd does there).  The two
 interpolation tables come from torch itself, once per engine (`pos_tables`).
+
+`dtype="bfloat16"` (default "float32": exact fp32 throughout) is the opt-in mixed-precision step of include/dvt_stage3.h
+(gemm_mode 1): the forward and data-gradient GEMMs of the blocks' four linear layers run on the extractor's bf16 MFMA GEMM with
+operands rounded to bf16; weight gradients, arenas, activations and everything that is not one of those GEMMs stay fp32.
 """
 from __future__ import annotations
 
@@ -38,7 +42,31 @@ _lib.register_signatures({
     "dvt_s3_param_offsets_pos": (_I, [C.POINTER(VitConfig), _I, C.POINTER(C.c_int64)]),
     "dvt_s3_workspace_bytes_pos": (C.c_int64, [C.POINTER(VitConfig), _I, _I]),
     "dvt_s3_train_slice_pos": (_I, [C.POINTER(VitConfig), _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, C.c_int64, _P, _P]),
+    "dvt_s3_workspace_bytes_mp": (C.c_int64, [C.POINTER(VitConfig), _I, _I, _I]),
+    "dvt_s3_train_slice_pos_mp": (_I, [C.POINTER(VitConfig), _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P, C.c_int64, _P,
+                                       _P]),
+    "dvt_s3_cast_bf16": (_I, [_P, _P, C.c_int64, _I, _P]),
+    "dvt_s3_cast_bf16_t": (_I, [_P, _P, _I, _I, _P]),
 })
+
+GEMM_MODES = {"float32": 0, "bfloat16": 1}  # Stage3Engine(dtype=) -> gemm_mode of dvt_s3_train_slice_pos_mp
+
+
+def cast_bf16(x: torch.Tensor) -> torch.Tensor:
+    """dvt_s3_cast_bf16 on its own: x fp32 [rows, n] (device, n % 4 == 0) -> bf16 [rows, n], round to nearest even."""
+    _lib.require_cuda(x)
+    y = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
+    _lib.check(_lib.lib().dvt_s3_cast_bf16(_lib.ptr(x), _lib.ptr(y), x.shape[0], x.shape[1], _lib.stream()), "dvt_s3_cast_bf16")
+    return y
+
+
+def cast_bf16_t(w: torch.Tensor) -> torch.Tensor:
+    """dvt_s3_cast_bf16_t on its own: w fp32 [n, k] (device, n % 64 == k % 64 == 0) -> bf16 [k, n], the rounded transpose."""
+    _lib.require_cuda(w)
+    wt = torch.empty(w.shape[1], w.shape[0], device=w.device, dtype=torch.bfloat16)
+    _lib.check(_lib.lib().dvt_s3_cast_bf16_t(_lib.ptr(w), _lib.ptr(wt), w.shape[0], w.shape[1], _lib.stream()),
+               "dvt_s3_cast_bf16_t")
+    return wt
 
 
 def make_config(dim: int, depth: int, patch: int, stride: int, img_h: int, img_w: int, n_reg: int = 0) -> VitConfig:
@@ -125,12 +153,15 @@ def param_layout(cfg: VitConfig, pos_grid: int | None = None):
 
 class Stage3Engine(FlatAdamW):
     def __init__(self, cfg: VitConfig, device: torch.device, pos_grid: int | None = None,
-                 max_work_bytes: int | None = None):
+                 max_work_bytes: int | None = None, dtype: str = "float32"):
         """`pos_grid`: the grid g0 of the checkpoint's position table when `pos_embed` is to keep its [1, cls + g0 g0, dim]
         shape and be resampled to the run's grid in every step; None: the table is at the run's grid (the layout and the
         calls without a resample).
         `max_work_bytes`: budget of the activation workspace (default: 80 % of the device memory free after the
-        arenas are allocated); `train_step` splits a batch into slices that fit."""
+        arenas are allocated); `train_step` splits a batch into slices that fit.
+        `dtype`: "float32" (exact fp32, the default) or "bfloat16": bf16 operands in the forward and data-gradient GEMMs of
+        the blocks' linear layers (see the module's docstring); the arenas and the checkpoint are fp32 either way."""
+        self.set_dtype(dtype)
         if torch.device(device).type != "cuda":
             raise _lib.DvtError("the stage-3 engine needs a HIP device; there is no CPU fallback")
         self.cfg = cfg
@@ -143,6 +174,14 @@ class Stage3Engine(FlatAdamW):
         self.loss = torch.zeros(4, device=self.device, dtype=torch.float32)
         self._slice_loss = torch.zeros(4, device=self.device, dtype=torch.float32)
         self.max_work_bytes = max_work_bytes
+
+    def set_dtype(self, dtype: str) -> None:
+        """Arithmetic of the following steps.  The state is fp32 either way, so the dtype may change between steps (the
+        interleaved A/B of tools/bench_stage3.py does); the workspace grows on demand."""
+        if dtype not in GEMM_MODES:
+            raise _lib.DvtError(f"the stage-3 step computes in {sorted(GEMM_MODES)}, got dtype={dtype!r}")
+        self.dtype = dtype
+        self.gemm_mode = GEMM_MODES[dtype]
 
     # ---- parameters -------------------------------------------------------------------------------
     def load_timm(self, state: dict) -> None:
@@ -170,13 +209,19 @@ class Stage3Engine(FlatAdamW):
 
     # ---- kernels ----------------------------------------------------------------------------------
     def workspace_bytes(self, batch: int) -> int:
-        if self.pos_grid is None:
+        if self.gemm_mode:
+            n = int(_lib.lib().dvt_s3_workspace_bytes_mp(C.byref(self.cfg), batch, self._g0(), self.gemm_mode))
+        elif self.pos_grid is None:
             n = int(_lib.lib().dvt_s3_workspace_bytes(C.byref(self.cfg), batch))
         else:
             n = int(_lib.lib().dvt_s3_workspace_bytes_pos(C.byref(self.cfg), batch, self.pos_grid))
         if n <= 0:
             raise _lib.DvtError("dvt_s3_workspace_bytes: invalid configuration")
         return n
+
+    def _g0(self) -> int:
+        """The table's grid for the `_mp` calls: `pos_grid`, or 0 for a table at the run's grid."""
+        return 0 if self.pos_grid is None else self.pos_grid
 
     def slice_size(self, batch: int) -> int:
         """Images per slice for a batch of `batch`: the largest count whose workspace fits the budget."""
@@ -215,6 +260,11 @@ class Stage3Engine(FlatAdamW):
         L = _lib.lib()
 
         def run_slice(im, tg, ft, n, loss):
+            if self.gemm_mode:
+                return L.dvt_s3_train_slice_pos_mp(C.byref(self.cfg), self._g0(), _lib.ptr(self._wy), _lib.ptr(self._wx),
+                                                   self.gemm_mode, _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(im),
+                                                   _lib.ptr(tg), _lib.ptr(ft), n, B, _lib.ptr(w), w.numel(), _lib.ptr(loss),
+                                                   _lib.stream())
             if self.pos_grid is None:
                 return L.dvt_s3_train_slice(C.byref(self.cfg), _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(im),
                                             _lib.ptr(tg), _lib.ptr(ft), n, B, _lib.ptr(w), w.numel(), _lib.ptr(loss),
@@ -223,13 +273,13 @@ class Stage3Engine(FlatAdamW):
                                             _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(im), _lib.ptr(tg),
                                             _lib.ptr(ft), n, B, _lib.ptr(w), w.numel(), _lib.ptr(loss), _lib.stream())
 
-        if mb >= B and self.pos_grid is None:
+        if mb >= B and self.pos_grid is None and not self.gemm_mode:
             _lib.check(L.dvt_s3_train_step(C.byref(self.cfg), _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(img),
                                            _lib.ptr(target), _lib.ptr(feat), B, _lib.ptr(w), w.numel(),
                                            _lib.ptr(self.loss), _lib.stream()), "dvt_s3_train_step")
             return self.loss
         if mb >= B:  # norm_batch == batch: the whole step
-            _lib.check(run_slice(img, target, feat, B, self.loss), "dvt_s3_train_slice_pos")
+            _lib.check(run_slice(img, target, feat, B, self.loss), "dvt_s3_train_slice_pos(_mp)")
             return self.loss
         l2 = torch.zeros((), device=self.device)
         cos = torch.zeros((), device=self.device)

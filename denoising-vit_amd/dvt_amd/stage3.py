@@ -28,6 +28,9 @@ Deviations, all forced or harmless:
   * `--grad_checkpointing` recomputes nothing: a batch that does not fit is split into slices (`--micro_batch`) whose
     gradients add up to the whole batch's.
   * PCA visualisations are not written (`--vis_freq` / `--num_vis_samples` are accepted).
+  * `--dtype bfloat16` (default float32, what the reference trains in) is an opt-in mixed-precision student step: see
+    dvt_amd/s3.py and include/dvt_stage3.h.  Parameters, optimizer state and checkpoints are fp32 either way, so a
+    checkpoint written under one dtype starts a run under the other through `--vit_checkpoint`.
   * the ViT weights come from `--vit_checkpoint` (a timm-layout state dict, or a stage-3 checkpoint) because timm cannot
     download here; `--allow_random_vit` runs on random weights (tests and plumbing only).
 """
@@ -242,6 +245,10 @@ def get_args(argv=None):
     p.add_argument("--micro_batch", type=int, default=0,
                    help="images per slice of the student's step; 0 = as many as fit in 80 %% of the free device memory")
     p.add_argument("--log_freq", default=50, type=int)
+    p.add_argument("--dtype", default="float32", choices=["float32", "bfloat16"],
+                   help="float32 (default): the student's step in exact fp32, as the reference trains.  bfloat16: the forward "
+                        "and data-gradient GEMMs of the blocks' linear layers take bf16 operands (fp32 accumulation); weight "
+                        "gradients, parameters, optimizer state, checkpoints and the teacher stay fp32")
     args = p.parse_args(argv)
     if isinstance(args.input_size, int):
         args.input_size = (args.input_size, args.input_size)
@@ -324,7 +331,7 @@ def build_models(args, device):
     if pos_grid is not None:
         print(f"stage 3: position table {g0} x {g0} resampled to {gh} x {gw} in every step", flush=True)
     student = Stage3Engine(make_config(dim, depth, patch, args.stride_size, *args.input_size, n_reg), device,
-                           pos_grid=pos_grid)
+                           pos_grid=pos_grid, dtype=args.dtype)
     student.load_timm(vit._state_dict)
     return student, teacher
 
@@ -343,6 +350,9 @@ def train(args, rank: int, world: int, device: torch.device, model_factory=None)
             print("stage 3: --grad_checkpointing recomputes nothing here; --micro_batch bounds the activation memory",
                   flush=True)
         print("stage 3: PCA visualisations are not written (--vis_freq / --num_vis_samples are accepted)", flush=True)
+        print(f"stage 3: student step dtype {args.dtype}"
+              + (" (bf16 operands in the forward and data-gradient GEMMs of the linear layers; weight gradients, state and "
+                 "checkpoints fp32)" if args.dtype == "bfloat16" else " (exact fp32)"), flush=True)
     misc.fix_random_seeds(args.seed)
     eng, teacher = (model_factory or build_models)(args, device)
     if distributed:  # DistributedDataParallel broadcasts rank 0's parameters at construction

@@ -16,6 +16,16 @@
  * for the backward pass, two-pass LayerNorm statistics, erf GELU.  Every block keeps its activations: about 0.18 GB per image
  * and block for ViT-B/14 at 518 x 518 (host code splits a batch that does not fit into slices, dvt_s3_train_slice).
  *
+ * Opt-in mixed precision (dvt_s3_train_slice_pos_mp, gemm_mode 1): of the three GEMMs of each of a block's four linear layers
+ * (qkv, proj, fc1, fc2), the forward y = x W^T + b and the data gradient dx = dy W run on the extractor's bf16 MFMA GEMM
+ * (csrc/dvt_vit_gemm.hip, fp32 accumulation, fp32 output) with BOTH operands rounded to bf16, round to nearest even: x and W
+ * for the forward, dy and W for the data gradient.  Nothing else changes: the weight and bias gradients dW = dy^T x, db are
+ * formed in exact fp32 from the unrounded dy and x (their reduction runs over the rows and has 9-36 output tiles: it would
+ * need a split-K bf16 kernel), every kept activation, the parameters, gradients and optimizer state, LayerNorm, LayerScale,
+ * GELU, the attention products and the softmax, the loss, the patch embedding, the position table's resample and the token
+ * assembly are fp32 as above.  A product of K terms then carries about 2^-9 sqrt(2) relative error per term instead of
+ * 2^-24: gradients agree with float64 to some 1e-2 relative L2 per tensor instead of 1e-5.  The default is exact fp32.
+ *
  * Conventions as in dvt_hip.h: int return codes (0 = ok, DVT_E_* / hipError_t otherwise), device pointers owned by the
  * caller, `stream` is a hipStream_t, nothing synchronises.
  */
@@ -97,6 +107,29 @@ int64_t dvt_s3_workspace_bytes_pos(const DvtVitConfig* cfg, int batch, int g0);
 int dvt_s3_train_slice_pos(const DvtVitConfig* cfg, int g0, const float* wy, const float* wx, const float* params,
                            float* grads, const float* img, const float* target, float* feat_out, int batch, int norm_batch,
                            void* work, int64_t work_bytes, float* loss_out, void* stream);
+
+/* ---- opt-in mixed precision (see "Arithmetic" at the top) -------------------------------------------------------------
+ * gemm_mode: 0 = exact fp32 (the call IS dvt_s3_train_slice_pos -- dvt_s3_train_slice for g0 = 0 -- and the workspace theirs),
+ *            1 = bf16 operands in the forward and data-gradient GEMMs of qkv / proj / fc1 / fc2, everything else as in 0.
+ * Mode 1 rounds the four weights of every block once per call into the workspace (as stored for the forward, transposed for
+ * the data gradient: params change between steps, and each slice rounds the same weights, so slices stay additive) and each
+ * A operand into one shared scratch right before its GEMM; the workspace grows by 4 bytes per block weight and
+ * 2 max(mlp_dim, 3 dim) bytes per token row, behind mode 0's carving.  g0 as for the _pos calls, or 0: the table is at the
+ * run's grid, the layout of dvt_s3_param_offsets and the step of dvt_s3_train_slice (wy, wx ignored).  DVT_E_BADARG (-1 for the
+ * size) before any launch: another gemm_mode, g0 < 0, a workspace below the mode's
+ * size, a null pointer, in mode 1 `params` or `work` not 16-byte aligned. */
+int64_t dvt_s3_workspace_bytes_mp(const DvtVitConfig* cfg, int batch, int g0, int gemm_mode);
+int dvt_s3_train_slice_pos_mp(const DvtVitConfig* cfg, int g0, const float* wy, const float* wx, int gemm_mode,
+                              const float* params, float* grads, const float* img, const float* target, float* feat_out,
+                              int batch, int norm_batch, void* work, int64_t work_bytes, float* loss_out, void* stream);
+
+/* The mode's casts, exported for tests (csrc/dvt_s3_cast.hip).  Round to nearest even on the bit pattern, as torch's
+ * .to(torch.bfloat16): denormals and the sign of zero are kept, a finite value beyond the bf16 range becomes infinity.
+ *   dvt_s3_cast_bf16:   x fp32 [rows, n] -> y bf16 [rows, n];  n % 4 == 0.
+ *   dvt_s3_cast_bf16_t: w fp32 [n, k]    -> wt bf16 [k, n] (the transpose);  n % 64 == k % 64 == 0.
+ * Pointers 16-byte aligned; DVT_E_BADARG otherwise, nothing launched. */
+int dvt_s3_cast_bf16(const float* x, void* y, int64_t rows, int n, void* stream);
+int dvt_s3_cast_bf16_t(const float* w, void* wt, int n, int k, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,5 @@
-"""Time the stage-3 student step (csrc/dvt_stage3.hip): forward + loss + backward + AdamW of a whole ViT in fp32.
+"""Time the stage-3 student step (csrc/dvt_stage3.hip): forward + loss + backward + AdamW of a whole ViT, in exact fp32 or
+in the opt-in bf16 mode (`--dtype bfloat16`: bf16 operands in the forward and data-gradient GEMMs of the linear layers).
 
 Prints one JSON line: ms per step, images/s, and the step's matrix FLOPs per second against the 157 TF/s fp32 MFMA peak
 of the MI355X.  The FLOPs count the student only (forward 1x, backward 2x; tokens padded to s_pad rows as the kernels
@@ -7,6 +8,13 @@ student's step) is not part of the timed step.
 
     python tools/bench_stage3.py [--dim 768 --depth 12 --img 518 --batch 64 --steps 3 --warmup 1]
                                  [--input_size H W] [--stride_size S] [--pos_grid G0]
+                                 [--dtype float32|bfloat16] [--ab N]
+
+`--ab N`: an interleaved A/B of the two dtypes in one process on one engine -- fp32 step, bf16 step, fp32 step, ... N of
+each after the warm-up of both, every step timed on its own (device synchronised on both sides).  The clock of the chip
+drifts over a run, so two runs one after the other do not compare; alternating steps see the same clock.  The JSON line then
+carries per dtype the median, minimum and maximum ms per step, and `bf16_faster_than_fp32_spread`: whether the bf16 median
+lies below the fp32 median by more than the fp32 leg's own min-max spread.
 
 `--input_size` / `--stride_size` set another geometry than `--img` square at stride 14; `--pos_grid G0` keeps the position
 table at G0 x G0 (37 for the DINOv2 checkpoints) and resamples it to the run's grid in every step, e.g.
@@ -49,19 +57,53 @@ def main():
     p.add_argument("--warmup", type=int, default=1)
     p.add_argument("--input_size", type=int, nargs=2, default=None, metavar=("H", "W"), help="default: --img square")
     p.add_argument("--stride_size", type=int, default=14)
+    p.add_argument("--dtype", default="float32", choices=["float32", "bfloat16"])
+    p.add_argument("--ab", type=int, default=0, metavar="N", help="interleaved fp32 / bf16 A/B, N timed steps of each")
     p.add_argument("--pos_grid", type=int, default=None,
                    help="grid of the position table when it is not the run's (resampled in every step); default: the run's")
     a = p.parse_args()
     dev = torch.device("cuda:0")
     H, W = a.input_size or (a.img, a.img)
     cfg = s3.make_config(a.dim, a.depth, 14, a.stride_size, H, W)
-    eng = s3.Stage3Engine(cfg, dev, pos_grid=a.pos_grid)
+    eng = s3.Stage3Engine(cfg, dev, pos_grid=a.pos_grid, dtype=a.dtype)
     n_pos = cfg.grid_h * cfg.grid_w if a.pos_grid is None else a.pos_grid ** 2
     eng.load_timm(random_state_dict(a.dim, a.depth, 14, 1 + n_pos, well_conditioned=True))
     g = torch.Generator(device=dev).manual_seed(0)
     img = torch.randn(a.batch, 3, H, W, device=dev, generator=g)
     tgt = torch.randn(a.batch, cfg.grid_h, cfg.grid_w, a.dim, device=dev, generator=g)
     mb = a.micro_batch or None
+    fl = step_flops(cfg, a.batch)
+    head = {"bench": "stage3_student_step", "dim": a.dim, "depth": a.depth, "img": a.img if a.input_size is None else [H, W],
+            "stride": a.stride_size, "grid": [cfg.grid_h, cfg.grid_w], "pos_grid": a.pos_grid, "batch": a.batch}
+    if a.ab > 0:
+        if mb is None:  # one slicing for both legs: what the larger (bf16) workspace allows
+            eng.set_dtype("bfloat16")
+            mb = eng.slice_size(a.batch)
+        ms = {"float32": [], "bfloat16": []}
+        for i in range(a.warmup + a.ab):
+            for dtype in ("float32", "bfloat16"):
+                eng.set_dtype(dtype)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                loss = eng.train_step(img, tgt, micro_batch=mb)
+                eng.adamw_step(1e-5, 1e-5)
+                torch.cuda.synchronize()
+                if i >= a.warmup:
+                    ms[dtype].append((time.perf_counter() - t0) * 1e3)
+        legs = {}
+        for dtype, v in ms.items():
+            v = sorted(v)
+            med = v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
+            legs[dtype] = {"median_ms": round(med, 2), "min_ms": round(v[0], 2), "max_ms": round(v[-1], 2),
+                           "images_per_s": round(a.batch / med * 1e3, 2), "tflops": round(fl / med / 1e9, 2)}
+        f32, b16 = legs["float32"], legs["bfloat16"]
+        print(json.dumps({**head, "mode": "interleaved_ab", "steps_each": a.ab, "slice": mb, "tflop_per_step": round(fl / 1e12, 2),
+                          "float32": f32, "bfloat16": b16, "speedup": round(f32["median_ms"] / b16["median_ms"], 3),
+                          "fp32_spread_ms": round(f32["max_ms"] - f32["min_ms"], 2),
+                          "bf16_faster_than_fp32_spread":
+                              bool(f32["median_ms"] - b16["median_ms"] > f32["max_ms"] - f32["min_ms"]),
+                          "loss": float(loss[0].cpu())}), flush=True)
+        return
     for _ in range(a.warmup):
         eng.train_step(img, tgt, micro_batch=mb)
         eng.adamw_step(1e-5, 1e-5)
@@ -72,9 +114,7 @@ def main():
         eng.adamw_step(1e-5, 1e-5)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
-    fl = step_flops(cfg, a.batch)
-    print(json.dumps({"bench": "stage3_student_step", "dim": a.dim, "depth": a.depth, "img": a.img if a.input_size is None else [H, W],
-                      "stride": a.stride_size, "grid": [cfg.grid_h, cfg.grid_w], "pos_grid": a.pos_grid, "batch": a.batch,
+    print(json.dumps({**head, "dtype": a.dtype,
                       "slice": eng.slice_size(a.batch) if mb is None else mb, "ms_per_step": round(dt * 1e3, 2),
                       "images_per_s": round(a.batch / dt, 3), "tflop_per_step": round(fl / 1e12, 2),
                       "tflops": round(fl / dt / 1e12, 2), "fraction_of_fp32_peak": round(fl / dt / PEAK_FP32, 3),
