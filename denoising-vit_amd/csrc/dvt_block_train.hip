@@ -1,12 +1,14 @@
-// Pieces of the stage-2 step that the stage-3 step (dvt_stage3.hip) runs as well: the row type of the row-local kernels,
-// LayerNorm backward, GELU, the fused attention-row kernels, the linear layers' forward / backward on the 128 x 128 x 32
-// exact-fp32 tile and the batched attention products.  Internal to the library (not part of the C ABI).
-//
-// Everything below lives in an anonymous namespace: each including translation unit gets its own copy of the kernels and of
-// the side stream with its two events (created once per process and translation unit).  The A/B switches are the process's,
-// defined in dvt_stage2.hip.
-#pragma once
-#include "dvt_common.h"
+// The transformer block's exact-fp32 training pieces that the stage-2 step (dvt_stage2.hip) and the stage-3 step
+// (dvt_stage3.hip) both run (dvt_block_train.h): LayerNorm backward, GELU, the fused attention-row kernels, the loss rows,
+// the linear layers' forward / backward on the 128 x 128 x 32 exact-fp32 tile, the batched attention products with the
+// attention forward / backward launch sequences around them, and the side stream those sequences fork onto.  One compiled
+// copy: what tests/test_gpu_parts.py drives through the dvt_parts_* forwarders at the end of this file is exactly what both
+// trainers launch.  The A/B switches are the process's, defined in dvt_stage2.hip.
+#include <map>
+#include <mutex>
+#include "dvt_block_train.h"
+#include "dvt_row_dev.h"
+#include "../../include/dvt_parts.h"
 
 // dvt_gemm_f32.hip: the fp32 extractor's 128 x 128 x 32 exact-fp32 MFMA tile (x . w^T + b, shapes per dvt_linear_big_ok)
 int dvt_linear_fwd_big(const float* x, const float* w, const float* b, float* y, int m, int n, int k, hipStream_t s);
@@ -14,55 +16,8 @@ bool dvt_linear_big_ok(int m, int n, int k);
 bool dvt_linear_wgrad_big_ok(int rows, int n, int k);
 int dvt_linear_wgrad_big(const float* dy, const float* x, float* dw, float* db, int rows, int n, int k, int accumulate,
                          hipStream_t s);
-extern int g_s2_fork_wgrad, g_s2_attn_rows, g_s2_fuse_softmax_bwd, g_s2_big_wgrad, g_s2_big_bwd, g_s2_big_fwd;
 
 namespace {
-
-#define S2_TRY(x)              \
-  do {                         \
-    const int rc__ = (x);      \
-    if (rc__ != 0) return rc__; \
-  } while (0)
-
-// ---- a row of C floats held by one wave: float4 index lane + 64 j, j < NJ -------------------------------
-template <int C>
-struct Row {
-  static constexpr int NJ = (C / 4 + 63) / 64;
-  float4 v[NJ];
-  __device__ __forceinline__ void load(const float* p, int lane) {
-    const float4* p4 = reinterpret_cast<const float4*>(p);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int i = lane + 64 * j;
-      v[j] = (i < C / 4) ? p4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
-  __device__ __forceinline__ void store(float* p, int lane) const {
-    float4* p4 = reinterpret_cast<float4*>(p);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int i = lane + 64 * j;
-      if (i < C / 4) p4[i] = v[j];
-    }
-  }
-  __device__ __forceinline__ void zero() {
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  __device__ __forceinline__ float sum() const {
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
-    return wave_sum(s);
-  }
-};
-#define ROW_FOR(j, NJ) _Pragma("unroll") for (int j = 0; j < NJ; ++j)
-
-__device__ __forceinline__ float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 f4_sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
-__device__ __forceinline__ float4 f4_mul(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-__device__ __forceinline__ float4 f4_scale(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
-__device__ __forceinline__ float f4_dot(float4 a, float4 b) { return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w); }
 
 // ==========================================================================================================
 // LayerNorm backward fused with the residual-path gradient:
@@ -166,7 +121,7 @@ __global__ __launch_bounds__(256) void s2_gelu_bwd_kernel(const float4* __restri
 // MODE 1, backward: dS = scale P (.) (dao v^T - D) in N-order, D = rowsum(dP (.) P) = dao . ao from s2_rowdot_kernel; P is
 //   read once (requested a tile ahead), dP never exists.
 // ==========================================================================================================
-constexpr int AR_Q = 128, AR_K = 32, AR_LD = 65;  // odd pitch: the 32 rows of a key-tile fragment read hit 32 banks
+constexpr int AR_K = 32, AR_LD = 65;  // odd pitch: the 32 rows of a key-tile fragment read hit 32 banks
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 template <int MODE>
@@ -328,13 +283,6 @@ __global__ __launch_bounds__(256) void s2_rowdot_kernel(const float* __restrict_
   }
 }
 
-template <typename K, typename... A>
-int launch_rows(K kernel, int R, hipStream_t s, A... args) {
-  hipLaunchKernelGGL(kernel, dim3(dvt_cdiv(R, 4)), dim3(256), 0, s, args...);
-  DVT_CHECK_LAUNCH();
-  return 0;
-}
-
 // ==========================================================================================================
 // Loss and its gradient over rows n_prefix <= t < T of every image, one wave per row (main_denoiser.py:213-217;
 // main_distillation.py: mse + 1 - cosine_similarity(dim=-1).mean()):
@@ -416,19 +364,119 @@ __global__ void s2_loss_finish_kernel(const float* __restrict__ acc, float* __re
   out[3] = 0.f;
 }
 
-// Clears acc, runs the two kernels above: dout and loss_out of `norm_batch` images' worth of loss rows (R rows are here).
+// out[k][n] = in[n][k] (n, k multiples of 32): 32 x 32 tiles through LDS, both sides in whole 128-B row pieces
+__global__ __launch_bounds__(256) void s2_transpose_kernel(const float* __restrict__ in, float* __restrict__ out, int n, int k) {
+  __shared__ float tile[32][33];
+  const int k0 = blockIdx.x * 32, n0 = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) tile[ty + 8 * i][tx] = in[(size_t)(n0 + ty + 8 * i) * k + k0 + tx];
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) out[(size_t)(k0 + ty + 8 * i) * n + n0 + tx] = tile[tx][ty + 8 * i];
+}
+
 template <bool ADD>
-int loss_rows(int C, const float* a, const float* b, const float* target, float* out, float* dout, float* acc, int n_prefix,
-              int T, int Tp, int R, int norm_batch, float* loss_out, hipStream_t s) {
+int loss_rows_t(int C, const float* a, const float* b, const float* target, float* out, float* dout, float* acc, int n_prefix,
+                int T, int Tp, int R, float inv_el, float inv_tok, hipStream_t s) {
+  switch (C) {
+    case 384: return launch_rows(s2_loss_kernel<384, ADD>, R, s, a, b, target, out, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok);
+    case 768: return launch_rows(s2_loss_kernel<768, ADD>, R, s, a, b, target, out, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok);
+    default: return launch_rows(s2_loss_kernel<1024, ADD>, R, s, a, b, target, out, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok);
+  }
+}
+
+int attn_rows(int mode, const float* rowop, int ld_row, const float* keyop, int ld_key, const float* P, const float* D, float* out,
+              int batch, int heads, int T, int Tp, float scale, hipStream_t s) {
+  const dim3 grid((Tp / AR_Q) * heads * batch), blk(256);
+  if (mode == 0)
+    hipLaunchKernelGGL(s2_attn_rows_kernel<0>, grid, blk, 0, s, rowop, ld_row, keyop, ld_key, (const float*)nullptr,
+                       (const float*)nullptr, out, heads, T, Tp, scale);
+  else
+    hipLaunchKernelGGL(s2_attn_rows_kernel<1>, grid, blk, 0, s, rowop, ld_row, keyop, ld_key, P, D, out, heads, T, Tp, scale);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
+int rowdot(const float* dO, const float* O, float* D, int R, int Tp, int C, hipStream_t s) {
+  return launch_rows(s2_rowdot_kernel, R, s, dO, O, D, R, Tp, C);
+}
+
+// One of the six (image, head)-batched attention products
+DvtGemmEx attn_gemm(const AttnDims& d, int layout, const float* A, int lda, long long sA0, long long sA1, const float* B,
+                    int ldb, long long sB0, long long sB1, float* Cc, int ldc, long long sC0, long long sC1, int M, int N,
+                    int K) {
+  DvtGemmEx g{};
+  g.layout = layout;
+  g.A = A; g.B = B; g.C = Cc;
+  g.M = M; g.N = N; g.K = K;
+  g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+  g.nb0 = d.batch; g.nb1 = d.heads;
+  g.sA0 = sA0; g.sA1 = sA1; g.sB0 = sB0; g.sB1 = sB1; g.sC0 = sC0; g.sC1 = sC1;
+  return g;
+}
+
+// batch strides (image, head) of the q / k / v columns of qkv, of P / dP, and of the per-head slices of an [R][C] tensor
+struct AttnStrides {
+  long long qs0, qs1, ps0, ps1, os0, os1;
+  explicit AttnStrides(const AttnDims& d)
+      : qs0((long long)d.Tp * 3 * d.C), qs1(64), ps0((long long)d.heads * d.Tp * d.Tp), ps1((long long)d.Tp * d.Tp),
+        os0((long long)d.Tp * d.C), os1(64) {}
+};
+
+}  // namespace
+
+struct SideStream {
+  hipStream_t stream;
+  hipEvent_t ev_fork, ev_join;
+};
+
+// the current device's side stream, or null: created whole or not at all (a later call tries again)
+static const SideStream* side_stream() {
+  static std::mutex lock;
+  static std::map<int, SideStream> per_device;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  std::lock_guard<std::mutex> hold(lock);
+  const auto it = per_device.find(dev);
+  if (it != per_device.end()) return &it->second;
+  SideStream n{};
+  if (hipStreamCreateWithFlags(&n.stream, hipStreamNonBlocking) == hipSuccess &&
+      hipEventCreateWithFlags(&n.ev_fork, hipEventDisableTiming) == hipSuccess &&
+      hipEventCreateWithFlags(&n.ev_join, hipEventDisableTiming) == hipSuccess)
+    return &per_device.emplace(dev, n).first->second;
+  if (n.ev_fork) (void)hipEventDestroy(n.ev_fork);
+  if (n.stream) (void)hipStreamDestroy(n.stream);
+  return nullptr;
+}
+
+BlockFork::BlockFork(hipStream_t s, bool want) : s_(s), side_((want && g_s2_fork_wgrad) ? side_stream() : nullptr) {}
+
+hipStream_t BlockFork::side() const { return side_ ? side_->stream : s_; }
+
+int BlockFork::fork() {
+  if (!side_) return 0;
+  hipError_t e = hipEventRecord(side_->ev_fork, s_);
+  if (e == hipSuccess) e = hipStreamWaitEvent(side_->stream, side_->ev_fork, 0);
+  open_ = open_ || e == hipSuccess;
+  return (int)e;
+}
+
+int BlockFork::join() {
+  if (!open_) return 0;
+  open_ = false;
+  hipError_t e = hipEventRecord(side_->ev_join, side_->stream);
+  if (e == hipSuccess) e = hipStreamWaitEvent(s_, side_->ev_join, 0);
+  return (int)e;
+}
+
+int loss_rows(bool add, int C, const float* a, const float* b, const float* target, float* out, float* dout, float* acc,
+              int n_prefix, int T, int Tp, int R, int norm_batch, float* loss_out, hipStream_t s) {
   const float N = (float)norm_batch * (float)(T - n_prefix);
   const float inv_el = 1.0f / (N * C), inv_tok = 1.0f / N;
   const hipError_t e = hipMemsetAsync(acc, 0, 64 * sizeof(float), s);
   if (e != hipSuccess) return (int)e;
-  switch (C) {
-    case 384: S2_TRY(launch_rows(s2_loss_kernel<384, ADD>, R, s, a, b, target, out, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok)); break;
-    case 768: S2_TRY(launch_rows(s2_loss_kernel<768, ADD>, R, s, a, b, target, out, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok)); break;
-    default: S2_TRY(launch_rows(s2_loss_kernel<1024, ADD>, R, s, a, b, target, out, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok)); break;
-  }
+  if (add) S2_TRY(loss_rows_t<true>(C, a, b, target, out, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok, s));
+  else S2_TRY(loss_rows_t<false>(C, a, b, target, out, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok, s));
   hipLaunchKernelGGL(s2_loss_finish_kernel, dim3(1), dim3(1), 0, s, (const float*)acc, loss_out, inv_el, inv_tok);
   DVT_CHECK_LAUNCH();
   return 0;
@@ -446,7 +494,18 @@ int ln_bwd(int C, const float* dy, const float* x, const float* mean, const floa
   return 0;
 }
 
-// y[R][n] = x[R][k] . w[n][k]^T + b
+int gelu_fwd(const float* h, float* a, int64_t n4, hipStream_t s) {
+  hipLaunchKernelGGL(s2_gelu_kernel, dim3(dvt_cdiv(n4, 256)), dim3(256), 0, s, (const float4*)h, (float4*)a, n4);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
+int gelu_bwd(const float* h, float* da, int64_t n4, hipStream_t s) {
+  hipLaunchKernelGGL(s2_gelu_bwd_kernel, dim3(dvt_cdiv(n4, 256)), dim3(256), 0, s, (const float4*)h, (float4*)da, n4);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
 int lin_fwd(const float* x, const float* w, const float* b, float* y, int R, int n, int k, hipStream_t s) {
   // round 6: the forward linear layers take the fp32 extractor's 128 x 128 x 32 tile where the shape allows (R = batch x 1408
   // rows, n and k multiples of 128 / 32: every layer of the Block) -- 125 against 97 TF/s; summation order differs only
@@ -459,48 +518,19 @@ int lin_fwd(const float* x, const float* w, const float* b, float* y, int R, int
   g.bias = b;
   return dvt_gemm_f32_ex(&g, s);
 }
-// side stream + fork / join events of lin_bwd (created once per process, never destroyed; one trainer per process and device)
-hipStream_t g_s2_side = nullptr;
-hipEvent_t g_s2_ev_fork = nullptr, g_s2_ev_join = nullptr;
-bool s2_side_stream(hipStream_t* out) {
-  if (g_s2_side == nullptr) {
-    if (hipStreamCreateWithFlags(&g_s2_side, hipStreamNonBlocking) != hipSuccess) return false;
-    if (hipEventCreateWithFlags(&g_s2_ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&g_s2_ev_join, hipEventDisableTiming) != hipSuccess)
-      return false;
-  }
-  *out = g_s2_side;
-  return true;
-}
 
-// out[k][n] = in[n][k] (n, k multiples of 32): 32 x 32 tiles through LDS, both sides in whole 128-B row pieces
-__global__ __launch_bounds__(256) void s2_transpose_kernel(const float* __restrict__ in, float* __restrict__ out, int n, int k) {
-  __shared__ float tile[32][33];
-  const int k0 = blockIdx.x * 32, n0 = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) tile[ty + 8 * i][tx] = in[(size_t)(n0 + ty + 8 * i) * k + k0 + tx];
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 4; ++i) out[(size_t)(k0 + ty + 8 * i) * n + n0 + tx] = tile[tx][ty + 8 * i];
-}
-
-// dx[R][k] = dy[R][n] . w[n][k];  dw[n][k] += dy^T . x;  db[n] += colsum(dy)
 // wT (round 6): scratch for w^T [k][n].  With it the data gradient is a FORWARD linear layer of the transposed weight --
 // dx = dy . (w^T)^T -- and takes the 128 x 128 x 32 tile (dvt_linear_fwd_big: both operands k-contiguous); the transposition is
 // 2 x 9 MB of traffic at most per layer, the GEMM 0.07-0.2 TFLOP.  Summation order differs from the 64 x 64 kernel only.
 int lin_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, float* db, int R, int n, int k,
-            hipStream_t s, float* wT = nullptr) {
+            hipStream_t s, float* wT) {
   // Round 6: the weight gradient and the data gradient of a layer are independent products of the same dy.  Their grids are a few
   // rounds of the chip's 512 workgroup slots each (2112 tiles = 4.1 rounds for the 768-wide outputs: the last round is 1/8
   // full), so the weight gradient goes to a side stream and the two fill each other's tails; joined before this returns (the
   // caller's next kernels overwrite dy / x).
-  hipStream_t sw = s;
-  const bool fork = g_s2_fork_wgrad && dx != nullptr && s2_side_stream(&sw);
-  if (fork) {
-    if (hipEventRecord(g_s2_ev_fork, s) != hipSuccess || hipStreamWaitEvent(sw, g_s2_ev_fork, 0) != hipSuccess) return DVT_E_BADARG;
-  } else {
-    sw = s;
-  }
+  BlockFork f(s, dx != nullptr);
+  S2_TRY(f.fork());
+  const hipStream_t sw = f.side();
   if (g_s2_big_wgrad && dvt_linear_wgrad_big_ok(R, n, k)) {  // round 6: the weight gradient on the 128 x 128 tile too
     S2_TRY(dvt_linear_wgrad_big(dy, x, dw, db, R, n, k, 1, sw));
   } else {
@@ -514,40 +544,122 @@ int lin_bwd(const float* dy, const float* x, const float* w, float* dx, float* d
     S2_TRY(dvt_gemm_f32_ex(&g, sw));
   }
   if (!dx) return 0;
-  int rc = 0;
   if (wT && g_s2_big_bwd && n % 32 == 0 && k % 32 == 0 && dvt_linear_big_ok(R, k, n)) {
     hipLaunchKernelGGL(s2_transpose_kernel, dim3(k / 32, n / 32), dim3(256), 0, s, w, wT, n, k);
     DVT_CHECK_LAUNCH();
-    rc = dvt_linear_fwd_big(dy, wT, nullptr, dx, R, k, n, s);
+    S2_TRY(dvt_linear_fwd_big(dy, wT, nullptr, dx, R, k, n, s));
   } else {
     DvtGemmEx d{};
     d.layout = 1;
     d.A = dy; d.B = w; d.C = dx;
     d.M = R; d.N = k; d.K = n;
     d.lda = n; d.ldb = k; d.ldc = k;
-    rc = dvt_gemm_f32_ex(&d, s);
+    S2_TRY(dvt_gemm_f32_ex(&d, s));
   }
-  if (fork && (hipEventRecord(g_s2_ev_join, sw) != hipSuccess || hipStreamWaitEvent(s, g_s2_ev_join, 0) != hipSuccess))
-    return DVT_E_BADARG;
-  return rc;
+  return f.join();
 }
 
-// The six (image, head)-batched attention products.  q/k/v live in qkv [R][3C] at column offsets 0 / C / 2C
-// (+ 64 head), P and dP are [batch*heads][Tp][Tp], per-head outputs are 64-column slices of [R][C] / [R][3C].
-struct AttnDims {
-  int batch, heads, Tp, C;
-};
-DvtGemmEx attn_gemm(const AttnDims& d, int layout, const float* A, int lda, long long sA0, long long sA1, const float* B,
-                    int ldb, long long sB0, long long sB1, float* Cc, int ldc, long long sC0, long long sC1, int M, int N,
-                    int K) {
+int block_attn_fwd(const AttnDims& d, const float* qkv, float* P, float* ao, float scale, bool rows_kernel, hipStream_t s) {
+  const int C = d.C, Tp = d.Tp;
+  const AttnStrides st(d);
   DvtGemmEx g{};
-  g.layout = layout;
-  g.A = A; g.B = B; g.C = Cc;
-  g.M = M; g.N = N; g.K = K;
-  g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.nb0 = d.batch; g.nb1 = d.heads;
-  g.sA0 = sA0; g.sA1 = sA1; g.sB0 = sB0; g.sB1 = sB1; g.sC0 = sC0; g.sC1 = sC1;
-  return g;
+  if (rows_kernel) {  // round 6: q k^T and the softmax in one kernel, P written once
+    S2_TRY(attn_rows(0, qkv, 3 * C, qkv + C, 3 * C, nullptr, nullptr, P, d.batch, d.heads, d.T, Tp, scale, s));
+  } else {
+    g = attn_gemm(d, 0, qkv, 3 * C, st.qs0, st.qs1, qkv + C, 3 * C, st.qs0, st.qs1, P, Tp, st.ps0, st.ps1, Tp, Tp, 64);
+    S2_TRY(dvt_gemm_f32_ex(&g, s));
+    S2_TRY(s2_softmax(P, d.T, Tp, (int64_t)d.batch * d.heads * Tp, scale, s));
+  }
+  g = attn_gemm(d, 1, P, Tp, st.ps0, st.ps1, qkv + 2 * C, 3 * C, st.qs0, st.qs1, ao, C, st.os0, st.os1, Tp, 64, Tp);
+  return dvt_gemm_f32_ex(&g, s);
 }
 
-}  // namespace
+int block_attn_bwd(const AttnDims& d, const float* qkv, const float* P, const float* ao, const float* dao, float* dqkv,
+                   float* dP, float* rowdot_buf, float scale, bool rows_kernel, bool fuse_softmax_bwd, hipStream_t s) {
+  const int C = d.C, Tp = d.Tp, R = d.batch * Tp;
+  const AttnStrides st(d);
+  // dV = P^T dao -- independent of the dS chain below (both read P and dao): on the side stream beside it (round 6, as the weight
+  // gradients in lin_bwd); dq and dk, two products of the same dS, likewise.  Joined before the caller's lin_bwd reads dqkv.
+  BlockFork f(s);
+  const hipStream_t sv = f.side();
+  S2_TRY(f.fork());
+  DvtGemmEx g = attn_gemm(d, 2, P, Tp, st.ps0, st.ps1, dao, C, st.os0, st.os1, dqkv + 2 * C, 3 * C, st.qs0, st.qs1, Tp, 64, Tp);
+  S2_TRY(dvt_gemm_f32_ex(&g, sv));
+  // dP = dao v^T, and the softmax backward dS = scale P (.) (dP - rowsum(dP (.) P)).  Round 6: rowsum(dP (.) P) = dao . ao per
+  // (image, head, query) comes from the two [R][C] tensors (s2_rowdot_kernel) and the backward is the EPILOGUE of the dP
+  // product -- dP is never written, P read once (before: 3 GB written + 9 GB read + 3 GB written by s2_softmax_bwd_kernel)
+  g = attn_gemm(d, 0, dao, C, st.os0, st.os1, qkv + 2 * C, 3 * C, st.qs0, st.qs1, dP, Tp, st.ps0, st.ps1, Tp, Tp, 64);
+  if (fuse_softmax_bwd && rows_kernel) {
+    S2_TRY(rowdot(dao, ao, rowdot_buf, R, Tp, C, s));
+    S2_TRY(attn_rows(1, dao, C, qkv + 2 * C, 3 * C, P, rowdot_buf, dP, d.batch, d.heads, d.T, Tp, scale, s));
+  } else if (fuse_softmax_bwd) {
+    S2_TRY(rowdot(dao, ao, rowdot_buf, R, Tp, C, s));
+    g.smul = P;
+    g.rowsub = rowdot_buf;
+    g.oscale = scale;
+    S2_TRY(dvt_gemm_f32_ex(&g, s));
+  } else {
+    S2_TRY(dvt_gemm_f32_ex(&g, s));
+    S2_TRY(s2_softmax_bwd(P, dP, Tp, (int64_t)d.batch * d.heads * Tp, scale, s));
+  }
+  // dq = dS k (main stream),  dk = dS^T q (side stream: behind dV there, and behind dS here)
+  S2_TRY(f.fork());
+  g = attn_gemm(d, 1, dP, Tp, st.ps0, st.ps1, qkv + C, 3 * C, st.qs0, st.qs1, dqkv, 3 * C, st.qs0, st.qs1, Tp, 64, Tp);
+  S2_TRY(dvt_gemm_f32_ex(&g, s));
+  g = attn_gemm(d, 2, dP, Tp, st.ps0, st.ps1, qkv, 3 * C, st.qs0, st.qs1, dqkv + C, 3 * C, st.qs0, st.qs1, Tp, 64, Tp);
+  S2_TRY(dvt_gemm_f32_ex(&g, sv));
+  return f.join();
+}
+
+// ---- component entry points for tests (include/dvt_parts.h): forwarders to the launchers above; no kernel and no launch of
+// their own, every check in front of the first launch ----
+extern "C" int dvt_parts_lin_fwd(const float* x, const float* w, const float* b, float* y, int R, int n, int k, void* stream) {
+  s2_read_env();
+  if (!x || !w || !y || R <= 0 || n <= 0 || k <= 0 || (n & 3) || (k & 3)) return DVT_E_BADARG;
+  if (!(g_s2_big_fwd && dvt_linear_big_ok(R, n, k)) && (k % 64)) return DVT_E_BADARG;  // dvt_gemm_f32_ex: whole k-tiles
+  return lin_fwd(x, w, b, y, R, n, k, (hipStream_t)stream);
+}
+
+extern "C" int dvt_parts_lin_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, float* db, float* wT,
+                                 int R, int n, int k, void* stream) {
+  s2_read_env();
+  if (!dy || !x || !dw || !db || (dx && !w) || R <= 0 || n <= 0 || k <= 0) return DVT_E_BADARG;
+  if ((n % 64) || (k % 64) || (R % 32)) return DVT_E_BADARG;
+  // the 64 x 64 weight-gradient kernel reduces over whole 64-row tiles, and so does the layout-1 data gradient's operand
+  if ((R % 64) && !(g_s2_big_wgrad && dvt_linear_wgrad_big_ok(R, n, k))) return DVT_E_BADARG;
+  return lin_bwd(dy, x, w, dx, dw, db, R, n, k, (hipStream_t)stream, wT);
+}
+
+extern "C" int dvt_parts_attn_rows(int mode, const float* rowop, int ld_row, const float* keyop, int ld_key, const float* P,
+                                   const float* D, float* out, int batch, int heads, int T, int Tp, float scale, void* stream) {
+  if ((mode != 0 && mode != 1) || !rowop || !keyop || !out || batch < 1 || heads < 1 || Tp < AR_Q || (Tp % AR_Q) || T < 1 || T > Tp)
+    return DVT_E_BADARG;
+  if (ld_row < heads * 64 || ld_key < heads * 64 || (ld_key & 3) || !dvt_aligned16(keyop) || (mode == 1 && (!P || !D)))
+    return DVT_E_BADARG;
+  if ((int64_t)(Tp / AR_Q) * heads * batch > 0x7fffffffLL) return DVT_E_BADARG;
+  return attn_rows(mode, rowop, ld_row, keyop, ld_key, P, D, out, batch, heads, T, Tp, scale, (hipStream_t)stream);
+}
+
+extern "C" int dvt_parts_rowdot(const float* dO, const float* O, float* D, int R, int Tp, int C, void* stream) {
+  if (!dO || !O || !D || R < 1 || Tp < 1 || (R % Tp) || C < 64 || (C % 64) || !dvt_aligned16(dO) || !dvt_aligned16(O)) return DVT_E_BADARG;
+  return rowdot(dO, O, D, R, Tp, C, (hipStream_t)stream);
+}
+
+extern "C" int dvt_parts_ln_bwd(int C, const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                                const float* dres, float* dx, float* dgamma, float* dbeta, int R, void* stream) {
+  if (!parts_c_ok(C) || !dy || !x || !mean || !rstd || !gamma || !dx || !dgamma || !dbeta || R < 1) return DVT_E_BADARG;
+  return ln_bwd(C, dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, R, (hipStream_t)stream);
+}
+
+extern "C" int dvt_parts_gelu(const float* h, float* a, int64_t n4, int backward, void* stream) {
+  if (!h || !a || n4 < 1 || !dvt_aligned16(h) || !dvt_aligned16(a) || (backward != 0 && backward != 1)) return DVT_E_BADARG;
+  return backward ? gelu_bwd(h, a, n4, (hipStream_t)stream) : gelu_fwd(h, a, n4, (hipStream_t)stream);
+}
+
+extern "C" int dvt_parts_loss_rows(int C, const float* a, const float* b, const float* target, float* out, float* dout, float* acc,
+                                   int n_prefix, int T, int Tp, int R, int norm_batch, float* loss_out, int add, void* stream) {
+  if (!parts_c_ok(C) || !a || !target || !dout || !acc || !loss_out || (add && !b) || (add != 0 && add != 1)) return DVT_E_BADARG;
+  if (n_prefix < 0 || T <= n_prefix || Tp < T || R < 1 || (R % Tp) || norm_batch < R / Tp) return DVT_E_BADARG;
+  return loss_rows(add != 0, C, a, add ? b : nullptr, target, out, dout, acc, n_prefix, T, Tp, R, norm_batch, loss_out,
+                   (hipStream_t)stream);
+}

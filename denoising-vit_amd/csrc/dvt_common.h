@@ -12,6 +12,7 @@
   } while (0)
 
 static inline int dvt_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+static inline bool dvt_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // Wave = 64 lanes on CDNA4; all reductions below are written for exactly that.
 __device__ __forceinline__ float wave_sum(float v) {

@@ -54,12 +54,10 @@ __global__ __launch_bounds__(256) void s3_cast_bf16_t_kernel(const float* __rest
   }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" int dvt_s3_cast_bf16(const float* x, void* y, int64_t rows, int n, void* stream) {
-  if (!x || !y || rows < 1 || n < 4 || n % 4 || !aligned16(x) || !aligned16(y)) return DVT_E_BADARG;
+  if (!x || !y || rows < 1 || n < 4 || n % 4 || !dvt_aligned16(x) || !dvt_aligned16(y)) return DVT_E_BADARG;
   const int64_t n4 = rows * n / 4;
   const int64_t blocks = (n4 + 255) / 256;
   // grid-stride over at most 8 workgroups per CU of the chip's 256
@@ -70,7 +68,7 @@ extern "C" int dvt_s3_cast_bf16(const float* x, void* y, int64_t rows, int n, vo
 }
 
 extern "C" int dvt_s3_cast_bf16_t(const float* w, void* wt, int n, int k, void* stream) {
-  if (!w || !wt || n < CT || k < CT || n % CT || k % CT || k / CT > 65535 || n / CT > 65535 || !aligned16(w) || !aligned16(wt))
+  if (!w || !wt || n < CT || k < CT || n % CT || k % CT || k / CT > 65535 || n / CT > 65535 || !dvt_aligned16(w) || !dvt_aligned16(wt))
     return DVT_E_BADARG;
   hipLaunchKernelGGL(s3_cast_bf16_t_kernel, dim3(k / CT, n / CT), dim3(256), 0, (hipStream_t)stream, w, (uint2*)wt, n, k);
   DVT_CHECK_LAUNCH();

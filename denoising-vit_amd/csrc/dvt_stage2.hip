@@ -6,9 +6,10 @@
 //
 // Everything is exact fp32, like the reference.  The contractions -- linear layers forward / data gradient /
 // weight gradient, and the four attention products per direction -- all go through ONE GEMM kernel family
-// (dvt_gemm_f32_ex, v_mfma_f32_32x32x2_f32 behind a 3-stage LDS-DMA pipeline); this file adds the row-local
-// pieces (LayerNorm forward/backward fused with the residual adds, softmax forward/backward, GELU, the loss
-// with its gradient, AdamW) and the launch sequence.  Attention keeps its probabilities P [batch*heads, Tp, Tp]
+// (dvt_gemm_f32_ex, v_mfma_f32_32x32x2_f32 behind a 3-stage LDS-DMA pipeline); the row-local pieces are
+// LayerNorm forward fused with the residual adds, softmax forward/backward and AdamW here, and LayerNorm backward, GELU, the
+// loss with its gradient and the attention launch sequences in dvt_block_train.hip, which the stage-3 step runs as well; this
+// file holds the step's launch sequence.  Attention keeps its probabilities P [batch*heads, Tp, Tp]
 // in HBM: at 288 GB per GPU the 3 GB that costs at batch 32 is cheaper than recomputing QK^T in the backward
 // pass, and P is exactly what dV = P^T dO and dS = P (dP - rowsum(P dP)) need.
 //
@@ -17,7 +18,9 @@
 // columns >= tokens get probability 0.
 #include <cstdlib>
 #include "dvt_common.h"
-#include "dvt_s2_parts.h"
+#include "dvt_block_train.h"
+#include "dvt_row_dev.h"
+#include "../../include/dvt_parts.h"
 #include "../../include/dvt_stage2.h"
 
 int g_s2_fork_wgrad = 1;  // DVT_S2_FORK_WGRAD=0 / dvt_tune_set(18, mask) bit 5: weight gradients on the caller's stream (A/B)
@@ -311,12 +314,9 @@ int run(const DvtS2Config* c, const float* params, float* grads, const float* x,
   offsets(c, &po);
   const int C = c->dim, F = c->mlp_dim, T = c->tokens, Tp = c->tokens_pad, H = c->heads, NB = c->n_blocks;
   const int R = batch * Tp;
-  const int64_t rowsP = (int64_t)batch * H * Tp;
   const float scale = 0.125f;  // head_dim^-0.5
   const bool attn_rows = g_s2_attn_rows && Tp % AR_Q == 0;  // s2_attn_rows_kernel walks whole blocks of 128 query rows
-  const AttnDims ad{batch, H, Tp, C};
-  const long long qs0 = (long long)Tp * 3 * C, qs1 = 64, ps0 = (long long)H * Tp * Tp, ps1 = (long long)Tp * Tp,
-                  os0 = (long long)Tp * C, os1 = 64;
+  const AttnDims ad{batch, H, T, Tp, C};
   auto P = [&](int b, int i) { return params + po.t[b][i]; };
   auto G = [&](int b, int i) { return grads + po.t[b][i]; };
 
@@ -327,29 +327,11 @@ int run(const DvtS2Config* c, const float* params, float* grads, const float* x,
     S2Block k = w.blk[b];
     if (!training && (b & 1)) k.xin = w.d0;  // inference with several blocks: block inputs ping-pong
     S2_TRY(lin_fwd(k.xn1, P(b, QKVW), P(b, QKVB), k.qkv, R, 3 * C, C, s));
-    {  // S = q k^T  ->  P = softmax(scale S)  ->  ao = P v
-      DvtGemmEx g{};
-      if (attn_rows) {  // round 6: q k^T and the softmax in one kernel, P written once
-        hipLaunchKernelGGL(s2_attn_rows_kernel<0>, dim3((Tp / AR_Q) * H * batch), dim3(256), 0, s, (const float*)k.qkv, 3 * C,
-                           (const float*)(k.qkv + C), 3 * C, (const float*)nullptr, (const float*)nullptr, k.P, H, T, Tp, scale);
-        DVT_CHECK_LAUNCH();
-      } else {
-        g = attn_gemm(ad, 0, k.qkv, 3 * C, qs0, qs1, k.qkv + C, 3 * C, qs0, qs1, k.P, Tp, ps0, ps1, Tp, Tp, 64);
-        S2_TRY(dvt_gemm_f32_ex(&g, s));
-        hipLaunchKernelGGL(s2_softmax_kernel, dim3(dvt_cdiv(rowsP, 4)), dim3(256), 0, s, k.P, T, Tp, rowsP, scale);
-        DVT_CHECK_LAUNCH();
-      }
-      g = attn_gemm(ad, 1, k.P, Tp, ps0, ps1, k.qkv + 2 * C, 3 * C, qs0, qs1, k.ao, C, os0, os1, Tp, 64, Tp);
-      S2_TRY(dvt_gemm_f32_ex(&g, s));
-    }
+    S2_TRY(block_attn_fwd(ad, k.qkv, k.P, k.ao, scale, attn_rows, s));  // P = softmax(scale q k^T), ao = P v
     S2_TRY(lin_fwd(k.ao, P(b, PROJW), P(b, PROJB), w.tmp, R, C, C, s));
     S2_TRY(add_ln(C, k.xin, 0, w.tmp, 0, k.x1, P(b, N2W), P(b, N2B), k.xn2, k.mean2, k.rstd2, T, Tp, R, c->ln_eps, s));
     S2_TRY(lin_fwd(k.xn2, P(b, FC1W), P(b, FC1B), k.h, R, F, C, s));
-    {
-      const int64_t n4 = (int64_t)R * F / 4;
-      hipLaunchKernelGGL(s2_gelu_kernel, dim3(dvt_cdiv(n4, 256)), dim3(256), 0, s, (const float4*)k.h, (float4*)k.a, n4);
-      DVT_CHECK_LAUNCH();
-    }
+    S2_TRY(gelu_fwd(k.h, k.a, (int64_t)R * F / 4, s));
     S2_TRY(lin_fwd(k.a, P(b, FC2W), P(b, FC2B), w.tmp, R, C, F, s));
     if (b + 1 < NB) {
       S2Block n = w.blk[b + 1];
@@ -369,64 +351,19 @@ int run(const DvtS2Config* c, const float* params, float* grads, const float* x,
   }
 
   // ---- loss ----
-  S2_TRY(loss_rows<true>(C, last.x1, w.tmp, target, pred, w.d0, w.acc, 0, T, Tp, R, batch, loss_out, s));
+  S2_TRY(loss_rows(true, C, last.x1, w.tmp, target, pred, w.d0, w.acc, 0, T, Tp, R, batch, loss_out, s));
 
   // ---- backward: d0 holds the gradient w.r.t. the current block's OUTPUT ----
   for (int b = NB - 1; b >= 0; --b) {
     const S2Block& k = w.blk[b];
     // mlp: out = x1 + fc2(gelu(fc1(norm2(x1))))
     S2_TRY(lin_bwd(w.d0, k.a, P(b, FC2W), w.dh, G(b, FC2W), G(b, FC2B), R, C, F, s, w.wT));
-    {
-      const int64_t n4 = (int64_t)R * F / 4;
-      hipLaunchKernelGGL(s2_gelu_bwd_kernel, dim3(dvt_cdiv(n4, 256)), dim3(256), 0, s, (const float4*)k.h, (float4*)w.dh, n4);
-      DVT_CHECK_LAUNCH();
-    }
+    S2_TRY(gelu_bwd(k.h, w.dh, (int64_t)R * F / 4, s));
     S2_TRY(lin_bwd(w.dh, k.xn2, P(b, FC1W), w.d2, G(b, FC1W), G(b, FC1B), R, F, C, s, w.wT));
     S2_TRY(ln_bwd(C, w.d2, k.x1, k.mean2, k.rstd2, P(b, N2W), w.d0, w.d1, G(b, N2W), G(b, N2B), R, s));  // d1 = d x1
     // attention: x1 = xin + proj(attn(norm1(xin)))
     S2_TRY(lin_bwd(w.d1, k.ao, P(b, PROJW), w.d2, G(b, PROJW), G(b, PROJB), R, C, C, s, w.wT));  // d2 = d ao
-    {
-      // dV = P^T dao -- independent of the dS chain below (both read P and dao): on the side stream beside it (round 6, as the weight
-      // gradients in lin_bwd); dq and dk, two products of the same dS, likewise.  Joined before lin_bwd reads dqkv.
-      hipStream_t sv = s;
-      const bool fork = g_s2_fork_wgrad && s2_side_stream(&sv);
-      if (!fork) sv = s;
-      if (fork && (hipEventRecord(g_s2_ev_fork, s) != hipSuccess || hipStreamWaitEvent(sv, g_s2_ev_fork, 0) != hipSuccess))
-        return DVT_E_BADARG;
-      DvtGemmEx g = attn_gemm(ad, 2, k.P, Tp, ps0, ps1, w.d2, C, os0, os1, w.dqkv + 2 * C, 3 * C, qs0, qs1, Tp, 64, Tp);
-      S2_TRY(dvt_gemm_f32_ex(&g, sv));
-      // dP = dao v^T, and the softmax backward dS = scale P (.) (dP - rowsum(dP (.) P)).  Round 6: rowsum(dP (.) P) = dao . ao per
-      // (image, head, query) comes from the two [R][C] tensors (s2_rowdot_kernel) and the backward is the EPILOGUE of the dP
-      // product -- dP is never written, P read once (before: 3 GB written + 9 GB read + 3 GB written by s2_softmax_bwd_kernel)
-      g = attn_gemm(ad, 0, w.d2, C, os0, os1, k.qkv + 2 * C, 3 * C, qs0, qs1, w.dP, Tp, ps0, ps1, Tp, Tp, 64);
-      if (g_s2_fuse_softmax_bwd && attn_rows) {
-        hipLaunchKernelGGL(s2_rowdot_kernel, dim3(dvt_cdiv(R, 4)), dim3(256), 0, s, (const float*)w.d2, (const float*)k.ao, w.rowdot, R, Tp, C);
-        DVT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(s2_attn_rows_kernel<1>, dim3((Tp / AR_Q) * H * batch), dim3(256), 0, s, (const float*)w.d2, C,
-                           (const float*)(k.qkv + 2 * C), 3 * C, (const float*)k.P, (const float*)w.rowdot, w.dP, H, T, Tp, scale);
-        DVT_CHECK_LAUNCH();
-      } else if (g_s2_fuse_softmax_bwd) {
-        hipLaunchKernelGGL(s2_rowdot_kernel, dim3(dvt_cdiv(R, 4)), dim3(256), 0, s, (const float*)w.d2, (const float*)k.ao, w.rowdot, R, Tp, C);
-        DVT_CHECK_LAUNCH();
-        g.smul = k.P;
-        g.rowsub = w.rowdot;
-        g.oscale = scale;
-        S2_TRY(dvt_gemm_f32_ex(&g, s));
-      } else {
-        S2_TRY(dvt_gemm_f32_ex(&g, s));
-        hipLaunchKernelGGL(s2_softmax_bwd_kernel, dim3(dvt_cdiv(rowsP, 4)), dim3(256), 0, s, (const float*)k.P, w.dP, Tp, rowsP, scale);
-        DVT_CHECK_LAUNCH();
-      }
-      // dq = dS k (main stream),  dk = dS^T q (side stream: behind dV there, and behind dS here)
-      if (fork && (hipEventRecord(g_s2_ev_fork, s) != hipSuccess || hipStreamWaitEvent(sv, g_s2_ev_fork, 0) != hipSuccess))
-        return DVT_E_BADARG;
-      g = attn_gemm(ad, 1, w.dP, Tp, ps0, ps1, k.qkv + C, 3 * C, qs0, qs1, w.dqkv, 3 * C, qs0, qs1, Tp, 64, Tp);
-      S2_TRY(dvt_gemm_f32_ex(&g, s));
-      g = attn_gemm(ad, 2, w.dP, Tp, ps0, ps1, k.qkv, 3 * C, qs0, qs1, w.dqkv + C, 3 * C, qs0, qs1, Tp, 64, Tp);
-      S2_TRY(dvt_gemm_f32_ex(&g, sv));
-      if (fork && (hipEventRecord(g_s2_ev_join, sv) != hipSuccess || hipStreamWaitEvent(s, g_s2_ev_join, 0) != hipSuccess))
-        return DVT_E_BADARG;
-    }
+    S2_TRY(block_attn_bwd(ad, k.qkv, k.P, k.ao, w.d2, w.dqkv, w.dP, w.rowdot, scale, attn_rows, g_s2_fuse_softmax_bwd != 0, s));
     S2_TRY(lin_bwd(w.dqkv, k.xn1, P(b, QKVW), w.d2, G(b, QKVW), G(b, QKVB), R, 3 * C, C, s, w.wT));
     S2_TRY(ln_bwd(C, w.d2, k.xin, k.mean1, k.rstd1, P(b, N1W), w.d1, w.d0, G(b, N1W), G(b, N1B), R, s));  // d0 = d xin
   }
@@ -461,7 +398,6 @@ extern "C" int64_t dvt_s2_workspace_bytes(const DvtS2Config* cfg, int batch, int
 // dvt_tune_set(18, mask): the same switches from inside a process (tests / A/B tools): bit 0 forward layers, 1 data gradients,
 // 2 weight gradients on the 128 x 128 tile, 3 softmax fused into the attention products, 4 softmax backward without a dP pass,
 // 5 weight gradients on a side stream beside the data gradients; 63 = default.  Results differ in summation order only.
-static void s2_read_env();
 int dvt_s2_tune(int mask) {
   if (mask < 0 || mask > 63) return DVT_E_BADARG;
   s2_read_env();  // (so that a later first call does not overwrite this)
@@ -474,7 +410,7 @@ int dvt_s2_tune(int mask) {
   return 0;
 }
 
-static void s2_read_env() {
+void s2_read_env() {
   static bool done = false;
   if (done) return;
   done = true;
@@ -519,63 +455,21 @@ extern "C" int dvt_adamw_step(float* params, float* grads, float* m, float* v, i
   return 0;
 }
 
-// ---- component entry points for tests (include/dvt_parts.h): forwarders to THIS translation unit's copy of the dvt_s2_parts.h
-// kernels and to the kernels above; no kernel and no launch of their own, every check in front of the first launch ----
-#include "../../include/dvt_parts.h"
-
-namespace {
-bool parts_c_ok(int C) { return C == 384 || C == 768 || C == 1024; }
-bool parts_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-}  // namespace
-
-extern "C" int dvt_parts_lin_fwd(const float* x, const float* w, const float* b, float* y, int R, int n, int k, void* stream) {
-  s2_read_env();
-  if (!x || !w || !y || R <= 0 || n <= 0 || k <= 0 || (n & 3) || (k & 3)) return DVT_E_BADARG;
-  if (!(g_s2_big_fwd && dvt_linear_big_ok(R, n, k)) && (k % 64)) return DVT_E_BADARG;  // dvt_gemm_f32_ex: whole k-tiles
-  return lin_fwd(x, w, b, y, R, n, k, (hipStream_t)stream);
-}
-
-extern "C" int dvt_parts_lin_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, float* db, float* wT,
-                                 int R, int n, int k, void* stream) {
-  s2_read_env();
-  if (!dy || !x || !dw || !db || (dx && !w) || R <= 0 || n <= 0 || k <= 0) return DVT_E_BADARG;
-  if ((n % 64) || (k % 64) || (R % 32)) return DVT_E_BADARG;
-  // the 64 x 64 weight-gradient kernel reduces over whole 64-row tiles, and so does the layout-1 data gradient's operand
-  if ((R % 64) && !(g_s2_big_wgrad && dvt_linear_wgrad_big_ok(R, n, k))) return DVT_E_BADARG;
-  return lin_bwd(dy, x, w, dx, dw, db, R, n, k, (hipStream_t)stream, wT);
-}
-
-extern "C" int dvt_parts_attn_rows(int mode, const float* rowop, int ld_row, const float* keyop, int ld_key, const float* P,
-                                   const float* D, float* out, int batch, int heads, int T, int Tp, float scale, void* stream) {
-  if ((mode != 0 && mode != 1) || !rowop || !keyop || !out || batch < 1 || heads < 1 || Tp < AR_Q || (Tp % AR_Q) || T < 1 || T > Tp)
-    return DVT_E_BADARG;
-  if (ld_row < heads * 64 || ld_key < heads * 64 || (ld_key & 3) || !parts_al16(keyop) || (mode == 1 && (!P || !D)))
-    return DVT_E_BADARG;
-  if ((int64_t)(Tp / AR_Q) * heads * batch > 0x7fffffffLL) return DVT_E_BADARG;
-  const dim3 grid((Tp / AR_Q) * heads * batch), blk(256);
-  hipStream_t s = (hipStream_t)stream;
-  if (mode == 0)
-    hipLaunchKernelGGL(s2_attn_rows_kernel<0>, grid, blk, 0, s, rowop, ld_row, keyop, ld_key, (const float*)nullptr,
-                       (const float*)nullptr, out, heads, T, Tp, scale);
-  else
-    hipLaunchKernelGGL(s2_attn_rows_kernel<1>, grid, blk, 0, s, rowop, ld_row, keyop, ld_key, P, D, out, heads, T, Tp, scale);
+// the two softmax passes of the unfused attention branches (dvt_block_train.h)
+int s2_softmax(float* S, int T, int Tp, int64_t rows, float scale, hipStream_t s) {
+  hipLaunchKernelGGL(s2_softmax_kernel, dim3(dvt_cdiv(rows, 4)), dim3(256), 0, s, S, T, Tp, rows, scale);
   DVT_CHECK_LAUNCH();
   return 0;
 }
 
-extern "C" int dvt_parts_rowdot(const float* dO, const float* O, float* D, int R, int Tp, int C, void* stream) {
-  if (!dO || !O || !D || R < 1 || Tp < 1 || (R % Tp) || C < 64 || (C % 64) || !parts_al16(dO) || !parts_al16(O)) return DVT_E_BADARG;
-  hipLaunchKernelGGL(s2_rowdot_kernel, dim3(dvt_cdiv(R, 4)), dim3(256), 0, (hipStream_t)stream, dO, O, D, R, Tp, C);
+int s2_softmax_bwd(const float* P, float* dP, int Tp, int64_t rows, float scale, hipStream_t s) {
+  hipLaunchKernelGGL(s2_softmax_bwd_kernel, dim3(dvt_cdiv(rows, 4)), dim3(256), 0, s, P, dP, Tp, rows, scale);
   DVT_CHECK_LAUNCH();
   return 0;
 }
 
-extern "C" int dvt_parts_ln_bwd(int C, const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
-                                const float* dres, float* dx, float* dgamma, float* dbeta, int R, void* stream) {
-  if (!parts_c_ok(C) || !dy || !x || !mean || !rstd || !gamma || !dx || !dgamma || !dbeta || R < 1) return DVT_E_BADARG;
-  return ln_bwd(C, dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, R, (hipStream_t)stream);
-}
-
+// ---- component entry points for tests (include/dvt_parts.h): forwarders to the kernels above; no kernel and no launch of
+// their own, every check in front of the first launch ----
 extern "C" int dvt_parts_add_ln(int C, const float* a, int a_packed, const float* b, int b_is_pos, float* sum_out,
                                 const float* gamma, const float* beta, float* xn, float* mean, float* rstd, int T, int Tp, int R,
                                 float eps, void* stream) {
@@ -584,37 +478,14 @@ extern "C" int dvt_parts_add_ln(int C, const float* a, int a_packed, const float
   return add_ln(C, a, a_packed, b, b_is_pos, sum_out, gamma, beta, xn, mean, rstd, T, Tp, R, eps, (hipStream_t)stream);
 }
 
-extern "C" int dvt_parts_gelu(const float* h, float* a, int64_t n4, int backward, void* stream) {
-  if (!h || !a || n4 < 1 || !parts_al16(h) || !parts_al16(a) || (backward != 0 && backward != 1)) return DVT_E_BADARG;
-  if (backward)
-    hipLaunchKernelGGL(s2_gelu_bwd_kernel, dim3(dvt_cdiv(n4, 256)), dim3(256), 0, (hipStream_t)stream, (const float4*)h, (float4*)a, n4);
-  else
-    hipLaunchKernelGGL(s2_gelu_kernel, dim3(dvt_cdiv(n4, 256)), dim3(256), 0, (hipStream_t)stream, (const float4*)h, (float4*)a, n4);
-  DVT_CHECK_LAUNCH();
-  return 0;
-}
-
 extern "C" int dvt_parts_softmax(const float* P, float* S, int T, int Tp, int64_t rows, float scale, int backward, void* stream) {
-  if (!S || Tp < 4 || (Tp & 3) || T < 1 || T > Tp || rows < 1 || !parts_al16(S) || (backward != 0 && backward != 1)) return DVT_E_BADARG;
-  if (backward && (!P || !parts_al16(P))) return DVT_E_BADARG;
-  if (backward)
-    hipLaunchKernelGGL(s2_softmax_bwd_kernel, dim3(dvt_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, P, S, Tp, rows, scale);
-  else
-    hipLaunchKernelGGL(s2_softmax_kernel, dim3(dvt_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, S, T, Tp, rows, scale);
-  DVT_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int dvt_parts_loss_rows(int C, const float* a, const float* b, const float* target, float* out, float* dout, float* acc,
-                                   int n_prefix, int T, int Tp, int R, int norm_batch, float* loss_out, int add, void* stream) {
-  if (!parts_c_ok(C) || !a || !target || !dout || !acc || !loss_out || (add && !b) || (add != 0 && add != 1)) return DVT_E_BADARG;
-  if (n_prefix < 0 || T <= n_prefix || Tp < T || R < 1 || (R % Tp) || norm_batch < R / Tp) return DVT_E_BADARG;
-  if (add) return loss_rows<true>(C, a, b, target, out, dout, acc, n_prefix, T, Tp, R, norm_batch, loss_out, (hipStream_t)stream);
-  return loss_rows<false>(C, a, nullptr, target, out, dout, acc, n_prefix, T, Tp, R, norm_batch, loss_out, (hipStream_t)stream);
+  if (!S || Tp < 4 || (Tp & 3) || T < 1 || T > Tp || rows < 1 || !dvt_aligned16(S) || (backward != 0 && backward != 1)) return DVT_E_BADARG;
+  if (backward && (!P || !dvt_aligned16(P))) return DVT_E_BADARG;
+  return backward ? s2_softmax_bwd(P, S, Tp, rows, scale, (hipStream_t)stream) : s2_softmax(S, T, Tp, rows, scale, (hipStream_t)stream);
 }
 
 extern "C" int dvt_parts_pos_grad(const float* dx, float* dpos, int batch, int T, int Tp, int C, void* stream) {
-  if (!dx || !dpos || batch < 1 || T < 1 || Tp < T || C < 4 || (C & 3) || !parts_al16(dx) || !parts_al16(dpos)) return DVT_E_BADARG;
+  if (!dx || !dpos || batch < 1 || T < 1 || Tp < T || C < 4 || (C & 3) || !dvt_aligned16(dx) || !dvt_aligned16(dpos)) return DVT_E_BADARG;
   const int64_t n = (int64_t)T * (C / 4);
   hipLaunchKernelGGL(s2_pos_grad_kernel, dim3(dvt_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, (const float4*)dx, (float4*)dpos,
                      batch, T, Tp, C / 4);

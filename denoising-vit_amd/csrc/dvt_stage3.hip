@@ -5,14 +5,16 @@
 //
 // The block is the stage-2 block (dvt_stage2.hip) with LayerScale: x1 = x + ls1 (.) proj(attn(norm1 x)), x2 = x1 + ls2 (.)
 // fc2(gelu(fc1(norm2 x1))).  Contractions, attention, GELU and the LayerNorm backward are the stage-2 pieces
-// (dvt_s2_parts.h); this file adds the patch embedding (im2col + GEMM, padded weight), the prefix-token / pos_embed assembly,
+// (dvt_block_train.hip); this file adds the patch embedding (im2col + GEMM, padded weight), the prefix-token / pos_embed assembly,
 // the LayerScale residual add fused with the following LayerNorm (the next block's norm1, or the final norm), the LayerScale
 // backward, the loss over the patch rows, and the assembly's backward.
 //
 // Rows: an image owns s_pad rows (prefix tokens, then patches, then zero padding).  Padded rows are zero in every activation
 // that feeds a reduction over rows, as in stage 2; the prefix rows take part in every block but not in the loss.
 #include "dvt_common.h"
-#include "dvt_s2_parts.h"
+#include "dvt_block_train.h"
+#include "dvt_row_dev.h"
+#include "../../include/dvt_parts.h"
 #include "../../include/dvt_stage2.h"
 #include "../../include/dvt_stage3.h"
 
@@ -157,8 +159,6 @@ int pos_pass(const float* in, float* out, const float* cls_in, float* cls_out, c
   DVT_CHECK_LAUNCH();
   return 0;
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // wy may be null only when g0 == gh, wx only when g0 == gw
 int pos_check(const float* wy, const float* wx, int g0, int gh, int gw, int dim, int has_cls) {
@@ -423,12 +423,6 @@ int ls_bwd(int C, const float* dy, const float* f, const float* ls, float* df, f
   return 0;
 }
 
-int fork_to(hipStream_t s, hipStream_t sv) {
-  if (sv == s) return 0;
-  if (hipEventRecord(g_s2_ev_fork, s) != hipSuccess || hipStreamWaitEvent(sv, g_s2_ev_fork, 0) != hipSuccess) return DVT_E_BADARG;
-  return 0;
-}
-
 // ---- gemm_mode 1: the forward and the data gradient of a linear layer on the extractor's bf16 GEMM (dvt_vit_gemm.hip, EPI_F32:
 // bf16 operands, fp32 accumulation, fp32 output; m % 128 == n % 128 == k % 64 == 0, which check_cfg guarantees for every
 // layer of the block: R = batch s_pad with s_pad % 128 == 0, dim in {384, 768, 1024}, mlp_dim % 128 == 0).  The A operand is
@@ -447,16 +441,12 @@ int lin_fwd_mp(const float* x, const uint16_t* wb, const float* b, float* y, int
 int lin_bwd_mp(const float* dy, const float* x, const uint16_t* wtb, float* dx, float* dw, float* db, int R, int n, int k,
                uint16_t* abf, hipStream_t s) {
   if (!mp_shape_ok(R, k, n)) return DVT_E_BADARG;
-  hipStream_t sw = s;
-  const bool fork = g_s2_fork_wgrad && s2_side_stream(&sw);
-  if (!fork) sw = s;
-  S2_TRY(fork_to(s, sw));
-  S2_TRY(lin_bwd(dy, x, nullptr, nullptr, dw, db, R, n, k, sw));  // no dx: the weight and bias gradients alone, on sw
+  BlockFork f(s);
+  S2_TRY(f.fork());
+  S2_TRY(lin_bwd(dy, x, nullptr, nullptr, dw, db, R, n, k, f.side()));  // no dx: the weight and bias gradients alone, beside
   S2_TRY(dvt_s3_cast_bf16(dy, abf, R, n, s));
   S2_TRY(dvt_vit_gemm_f32out(abf, wtb, nullptr, dx, R, k, n, s));
-  if (fork && (hipEventRecord(g_s2_ev_join, sw) != hipSuccess || hipStreamWaitEvent(s, g_s2_ev_join, 0) != hipSuccess))
-    return DVT_E_BADARG;
-  return 0;
+  return f.join();
 }
 
 int run(const DvtVitConfig* c, const float* params, float* grads, const float* img, const float* target, float* feat,
@@ -469,16 +459,14 @@ int run(const DvtVitConfig* c, const float* params, float* grads, const float* i
   if (!params || !grads || !img || !target || !loss_out || !work || batch < 1 || norm_batch < batch) return DVT_E_BADARG;
   S3Work w;
   if (carve(c, batch, reinterpret_cast<char*>(work), &w, g0, mode) > work_bytes) return DVT_E_BADARG;
-  if (mode == 1 && (!aligned16(params) || !aligned16(work))) return DVT_E_BADARG;  // (the casts move 16-byte pieces)
+  if (mode == 1 && (!dvt_aligned16(params) || !dvt_aligned16(work))) return DVT_E_BADARG;  // (the casts move 16-byte pieces)
   int64_t po[8 + DVT_S3_TENSORS_PER_BLOCK * DVT_VIT_MAX_DEPTH];
   offsets(c, po, g0);
   const int C = c->dim, F = c->mlp_dim, T = c->n_tokens, Tp = c->s_pad, H = c->heads, NB = c->depth;
   const int K0 = 3 * c->patch * c->patch, KP = c->k_patch;
   const int R = batch * Tp;
   const float scale = 0.125f;  // head_dim^-0.5
-  const AttnDims ad{batch, H, Tp, C};
-  const long long qs0 = (long long)Tp * 3 * C, qs1 = 64, ps0 = (long long)H * Tp * Tp, ps1 = (long long)Tp * Tp,
-                  os0 = (long long)Tp * C, os1 = 64;
+  const AttnDims ad{batch, H, T, Tp, C};
   auto P = [&](int b, int i) { return params + po[BLK0 + DVT_S3_TENSORS_PER_BLOCK * b + i]; };
   auto G = [&](int b, int i) { return grads + po[BLK0 + DVT_S3_TENSORS_PER_BLOCK * b + i]; };
   const int64_t normw = po[BLK0 + DVT_S3_TENSORS_PER_BLOCK * NB], normb = po[BLK0 + DVT_S3_TENSORS_PER_BLOCK * NB + 1];
@@ -520,19 +508,11 @@ int run(const DvtVitConfig* c, const float* params, float* grads, const float* i
   for (int b = 0; b < NB; ++b) {
     const S3Block& k = w.blk[b];
     S2_TRY(fwd(b, QKVW, WQKV, k.xn1, k.qkv, 3 * C, C));
-    hipLaunchKernelGGL(s2_attn_rows_kernel<0>, dim3((Tp / AR_Q) * H * batch), dim3(256), 0, s, (const float*)k.qkv, 3 * C,
-                       (const float*)(k.qkv + C), 3 * C, (const float*)nullptr, (const float*)nullptr, k.P, H, T, Tp, scale);
-    DVT_CHECK_LAUNCH();
-    DvtGemmEx g = attn_gemm(ad, 1, k.P, Tp, ps0, ps1, k.qkv + 2 * C, 3 * C, qs0, qs1, k.ao, C, os0, os1, Tp, 64, Tp);
-    S2_TRY(dvt_gemm_f32_ex(&g, s));
+    S2_TRY(block_attn_fwd(ad, k.qkv, k.P, k.ao, scale, true, s));  // (s_pad % 128 == 0: always the attention-row kernel)
     S2_TRY(fwd(b, PROJW, WPROJ, k.ao, k.f1, C, C));
     S2_TRY(ls_add_ln(C, k.xin, k.f1, P(b, LS1), k.x1, P(b, N2W), P(b, N2B), k.xn2, k.mean2, k.rstd2, T, Tp, R, c->ln_eps, s));
     S2_TRY(fwd(b, FC1W, WFC1, k.xn2, k.h, F, C));
-    {
-      const int64_t n4 = (int64_t)R * F / 4;
-      hipLaunchKernelGGL(s2_gelu_kernel, dim3(dvt_cdiv(n4, 256)), dim3(256), 0, s, (const float4*)k.h, (float4*)k.a, n4);
-      DVT_CHECK_LAUNCH();
-    }
+    S2_TRY(gelu_fwd(k.h, k.a, (int64_t)R * F / 4, s));
     S2_TRY(fwd(b, FC2W, WFC2, k.a, k.f2, C, F));
     if (b + 1 < NB) {
       const S3Block& n = w.blk[b + 1];
@@ -545,7 +525,7 @@ int run(const DvtVitConfig* c, const float* params, float* grads, const float* i
   }
 
   // ---- loss over the patch rows ----
-  S2_TRY(loss_rows<false>(C, w.xf, nullptr, target, feat, w.d1, w.acc, c->n_prefix, T, Tp, R, norm_batch, loss_out, s));
+  S2_TRY(loss_rows(false, C,w.xf, nullptr, target, feat, w.d1, w.acc, c->n_prefix, T, Tp, R, norm_batch, loss_out, s));
   // final norm: d0 = d xl
   S2_TRY(ln_bwd(C, w.d1, w.xl, w.meanf, w.rstdf, params + normw, nullptr, w.d0, grads + normw, grads + normb, R, s));
 
@@ -555,38 +535,14 @@ int run(const DvtVitConfig* c, const float* params, float* grads, const float* i
     // mlp: out = x1 + ls2 (.) fc2(gelu(fc1(norm2(x1))))
     S2_TRY(ls_bwd(C, w.d0, k.f2, P(b, LS2), w.d1, G(b, LS2), R, s));  // d1 = d f2
     S2_TRY(bwd(b, FC2W, WFC2, w.d1, k.a, w.dh, C, F));
-    {
-      const int64_t n4 = (int64_t)R * F / 4;
-      hipLaunchKernelGGL(s2_gelu_bwd_kernel, dim3(dvt_cdiv(n4, 256)), dim3(256), 0, s, (const float4*)k.h, (float4*)w.dh, n4);
-      DVT_CHECK_LAUNCH();
-    }
+    S2_TRY(gelu_bwd(k.h, w.dh, (int64_t)R * F / 4, s));
     S2_TRY(bwd(b, FC1W, WFC1, w.dh, k.xn2, w.d2, F, C));
     S2_TRY(ln_bwd(C, w.d2, k.x1, k.mean2, k.rstd2, P(b, N2W), w.d0, w.d1, G(b, N2W), G(b, N2B), R, s));  // d1 = d x1
     // attention: x1 = xin + ls1 (.) proj(attn(norm1(xin)))
     S2_TRY(ls_bwd(C, w.d1, k.f1, P(b, LS1), w.d0, G(b, LS1), R, s));  // d0 = d f1
     S2_TRY(bwd(b, PROJW, WPROJ, w.d0, k.ao, w.d2, C, C));  // d2 = d ao
-    {
-      // as the stage-2 step: dV = P^T dao on the side stream beside the dS chain, dS = scale P (.) (dao v^T - rowsum) in the
-      // attention-row kernel, then dq = dS k here and dk = dS^T q on the side stream; joined before lin_bwd reads dqkv
-      hipStream_t sv = s;
-      const bool fork = g_s2_fork_wgrad && s2_side_stream(&sv);
-      if (!fork) sv = s;
-      S2_TRY(fork_to(s, sv));
-      DvtGemmEx g = attn_gemm(ad, 2, k.P, Tp, ps0, ps1, w.d2, C, os0, os1, w.dqkv + 2 * C, 3 * C, qs0, qs1, Tp, 64, Tp);
-      S2_TRY(dvt_gemm_f32_ex(&g, sv));
-      hipLaunchKernelGGL(s2_rowdot_kernel, dim3(dvt_cdiv(R, 4)), dim3(256), 0, s, (const float*)w.d2, (const float*)k.ao, w.rowdot, R, Tp, C);
-      DVT_CHECK_LAUNCH();
-      hipLaunchKernelGGL(s2_attn_rows_kernel<1>, dim3((Tp / AR_Q) * H * batch), dim3(256), 0, s, (const float*)w.d2, C,
-                         (const float*)(k.qkv + 2 * C), 3 * C, (const float*)k.P, (const float*)w.rowdot, w.dP, H, T, Tp, scale);
-      DVT_CHECK_LAUNCH();
-      S2_TRY(fork_to(s, sv));
-      g = attn_gemm(ad, 1, w.dP, Tp, ps0, ps1, k.qkv + C, 3 * C, qs0, qs1, w.dqkv, 3 * C, qs0, qs1, Tp, 64, Tp);
-      S2_TRY(dvt_gemm_f32_ex(&g, s));
-      g = attn_gemm(ad, 2, w.dP, Tp, ps0, ps1, k.qkv, 3 * C, qs0, qs1, w.dqkv + C, 3 * C, qs0, qs1, Tp, 64, Tp);
-      S2_TRY(dvt_gemm_f32_ex(&g, sv));
-      if (fork && (hipEventRecord(g_s2_ev_join, sv) != hipSuccess || hipStreamWaitEvent(s, g_s2_ev_join, 0) != hipSuccess))
-        return DVT_E_BADARG;
-    }
+    // as the stage-2 step, always with dS from the attention-row kernel (bits 3 and 4 of dvt_tune_set(18, .) are stage 2's)
+    S2_TRY(block_attn_bwd(ad, k.qkv, k.P, k.ao, w.d2, w.dqkv, w.dP, w.rowdot, scale, true, true, s));
     S2_TRY(bwd(b, QKVW, WQKV, w.dqkv, k.xn1, w.d2, 3 * C, C));
     S2_TRY(ln_bwd(C, w.d2, k.xin, k.mean1, k.rstd1, P(b, N1W), w.d1, w.d0, G(b, N1W), G(b, N1B), R, s));  // d0 = d xin
   }
@@ -646,14 +602,14 @@ extern "C" int dvt_s3_train_step(const DvtVitConfig* cfg, const float* params, f
 extern "C" int dvt_pos_resample_fwd(const float* pos, float* out, const float* wy, const float* wx, float* tmp, int g0,
                                     int grid_h, int grid_w, int dim, int has_cls, void* stream) {
   S2_TRY(pos_check(wy, wx, g0, grid_h, grid_w, dim, has_cls));
-  if (!pos || !out || !tmp || !aligned16(pos) || !aligned16(out) || !aligned16(tmp)) return DVT_E_BADARG;
+  if (!pos || !out || !tmp || !dvt_aligned16(pos) || !dvt_aligned16(out) || !dvt_aligned16(tmp)) return DVT_E_BADARG;
   return pos_resample_fwd(pos, out, wy, wx, tmp, g0, grid_h, grid_w, dim, has_cls, (hipStream_t)stream);
 }
 
 extern "C" int dvt_pos_resample_bwd(const float* dout, float* dpos, const float* wy, const float* wx, float* tmp, int g0,
                                     int grid_h, int grid_w, int dim, int has_cls, void* stream) {
   S2_TRY(pos_check(wy, wx, g0, grid_h, grid_w, dim, has_cls));
-  if (!dout || !dpos || !tmp || !aligned16(dout) || !aligned16(dpos) || !aligned16(tmp)) return DVT_E_BADARG;
+  if (!dout || !dpos || !tmp || !dvt_aligned16(dout) || !dvt_aligned16(dpos) || !dvt_aligned16(tmp)) return DVT_E_BADARG;
   return pos_resample_bwd(dout, dpos, wy, wx, tmp, g0, grid_h, grid_w, dim, has_cls, (hipStream_t)stream);
 }
 
@@ -693,10 +649,7 @@ extern "C" int dvt_s3_train_slice_pos(const DvtVitConfig* cfg, int g0, const flo
 
 // ---- component entry points for tests (include/dvt_parts.h): forwarders to the kernels above; no kernel and no launch of their
 // own, every check in front of the launch ----
-#include "../../include/dvt_parts.h"
-
 namespace {
-bool parts_c_ok(int C) { return C == 384 || C == 768 || C == 1024; }
 // the fields the assembly / im2col kernels read, the rest zero
 int parts_cfg(DvtVitConfig* c, int dim, int n_prefix, int n_tokens, int s_pad, int pos_has_cls) {
   if (dim < 4 || (dim & 3) || n_prefix < 0 || n_tokens <= n_prefix || s_pad < n_tokens || (pos_has_cls != 0 && pos_has_cls != 1))
@@ -729,7 +682,7 @@ extern "C" int dvt_parts_s3_embed(const float* y, float* x, const float* prefix,
                                   int n_tokens, int s_pad, int pos_has_cls, void* stream) {
   DvtVitConfig c;
   S2_TRY(parts_cfg(&c, dim, n_prefix, n_tokens, s_pad, pos_has_cls));
-  if (!y || !x || !pos || (n_prefix > 0 && !prefix) || batch < 1 || !aligned16(y) || !aligned16(x) || !aligned16(prefix) || !aligned16(pos))
+  if (!y || !x || !pos || (n_prefix > 0 && !prefix) || batch < 1 || !dvt_aligned16(y) || !dvt_aligned16(x) || !dvt_aligned16(prefix) || !dvt_aligned16(pos))
     return DVT_E_BADARG;
   hipLaunchKernelGGL(s3_embed_kernel, dim3(batch * s_pad), dim3(256), 0, (hipStream_t)stream, (const float4*)y, (float4*)x,
                      (const float4*)prefix, (const float4*)pos, c);
@@ -741,7 +694,7 @@ extern "C" int dvt_parts_s3_embed_bwd(float* dx, float* dprefix, float* dpos, in
                                       int s_pad, int pos_has_cls, void* stream) {
   DvtVitConfig c;
   S2_TRY(parts_cfg(&c, dim, n_prefix, n_tokens, s_pad, pos_has_cls));
-  if (!dx || !dpos || (n_prefix > 0 && !dprefix) || batch < 1 || !aligned16(dx) || !aligned16(dprefix) || !aligned16(dpos))
+  if (!dx || !dpos || (n_prefix > 0 && !dprefix) || batch < 1 || !dvt_aligned16(dx) || !dvt_aligned16(dprefix) || !dvt_aligned16(dpos))
     return DVT_E_BADARG;
   const int64_t n = (int64_t)n_tokens * (dim / 4);
   hipLaunchKernelGGL(s3_embed_bwd_kernel, dim3(dvt_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, (float4*)dx, (float4*)dprefix,

@@ -28,6 +28,7 @@ HIP_SOURCES = [
     "dvt_vit_attn.hip",
     "dvt_vit_f32.hip",
     "dvt_denoiser.hip",
+    "dvt_block_train.hip",
     "dvt_stage2.hip",
     "dvt_stage3.hip",
     "dvt_s3_cast.hip",
@@ -265,6 +266,8 @@ def build(force: bool = False, verbose: bool = False, lab: bool = False) -> Path
     source, compiled in parallel, then one link.  Rebuilds only when a source/header is newer than the library.
     The bf16 ViT extractor is three of those sources -- dvt_vit.hip (forward loop, small kernels), dvt_vit_gemm.hip (GEMMs; its
     epilogues in dvt_vit_epilogue.h) and dvt_vit_attn.hip (attention) -- that share dvt_vit_dev.h and compile side by side.
+    The stage-2 and stage-3 trainers (dvt_stage2.hip, dvt_stage3.hip) share one compiled copy of their block code,
+    dvt_block_train.hip (declared in dvt_block_train.h).
     lab=True builds the DEVELOPER library csrc/libdvt_hip_lab.so with -DDVT_LAB (superseded schedules, experiments and
     timing builds of csrc/lab/); nothing in dvt_amd loads it (tools/build_lab.py, tools/lab_*.py, tests/test_gpu_lab.py)."""
     from concurrent.futures import ThreadPoolExecutor

@@ -8,9 +8,9 @@
  * launch.  It validates pointers and shapes and returns DVT_E_BADARG (-1) before any launch, takes a hipStream_t as
  * `void* stream` and does not synchronise.  All pointers are device pointers, 16-byte aligned, fp32 unless said otherwise.
  *
- * dvt_stage2.hip and dvt_stage3.hip each compile their OWN copy of the kernels of csrc/dvt_s2_parts.h (an anonymous
- * namespace in a header), from the same source with the same flags.  The dvt_parts_* functions of that header reach the
- * copy in dvt_stage2.hip; the copy in dvt_stage3.hip is tied down by the stage-3 step tests.
+ * The block code that the stage-2 and the stage-3 step share is compiled once, in csrc/dvt_block_train.hip: its
+ * dvt_parts_* functions reach the one copy of those kernels and launchers, so tests/test_gpu_parts.py holds exactly what
+ * both trainers launch.
  *
  * Developer instrumentation in the class of dvt_tune_set: not API, ABI version unchanged.
  */
@@ -56,7 +56,7 @@ int dvt_parts_gemm_ex(const DvtPartsGemmEx* g, void* stream);
 int dvt_parts_linear_big_epi(const float* x, const float* w, const float* b, float* y, int m, int n, int k, int epi,
                              const float* gamma, void* stream);
 
-/* ---- dvt_stage2.hip (its copy of csrc/dvt_s2_parts.h) ------------------------------------------------------ */
+/* ---- dvt_block_train.hip (lin_fwd .. loss_rows, shared by stages 2 and 3) and dvt_stage2.hip (add_ln, softmax, pos_grad) -- */
 /* lin_fwd / lin_bwd exactly as the trainers call them; both obey dvt_tune_set(18, mask), the side-stream fork of the
  * weight gradient included (joined before the call returns to the caller's stream order).
  *   y[R][n] = x[R][k] . w[n][k]^T + b

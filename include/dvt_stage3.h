@@ -11,7 +11,7 @@
  * Configuration: DvtVitConfig (include/dvt_vit.h) as dvt_vit_config / dvt_vit_config_reg write it; s_pad must be a multiple
  * of 128 (the attention row kernels walk whole blocks of 128 queries), dim 384 / 768 / 1024, heads = dim / 64.
  *
- * Arithmetic: exact fp32 throughout, on the kernels of the stage-2 step (csrc/dvt_s2_parts.h): linear layers on the
+ * Arithmetic: exact fp32 throughout, on the block code shared with the stage-2 step (csrc/dvt_block_train.hip): linear layers on the
  * 128 x 128 x 32 exact-fp32 MFMA tile, the softmax fused into the two [s_pad][s_pad] attention products, probabilities kept
  * for the backward pass, two-pass LayerNorm statistics, erf GELU.  Every block keeps its activations: about 0.18 GB per image
  * and block for ViT-B/14 at 518 x 518 (host code splits a batch that does not fit into slices, dvt_s3_train_slice).

@@ -1,6 +1,8 @@
 """GPU: stage-2 (N3) parity through the C ABI -- `Denoiser` forward, the fused forward+loss+backward step, AdamW
 and a short training run against the CPU oracle (oracle/stage2.py: timm-Block restatement + torch autograd +
 torch.optim.AdamW) on identical parameters and batches.  fp32 on both sides; tolerances are relative L2."""
+import importlib.util
+import json
 import math
 import os
 
@@ -13,6 +15,7 @@ from oracle import vit as OV
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def rel(a, b):
@@ -103,6 +106,40 @@ def test_step_kernel_choices_agree(built_lib):
         print(f"[stage-2 kernel choices] mask {mask:2d}: gradient arena rel-L2 vs round 5's flow {r:.2e}")
         assert r < 5e-6, (mask, r)
     assert not torch.equal(out[63][1], base_g)  # (the choices really are different kernels)
+
+
+def _recorder(name):
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.mark.parametrize("case", ["rows11x11", "gemm7x7", "mask0_11x11", "forward5x9"])
+def test_step_keeps_the_parents_bits(golden_dir, case):
+    """One step (or forward) per kernel choice of the block code shared with stage 3 -- the attention-row kernel with forks at
+    11 x 11, the GEMM + softmax forward and the softmax backward as a GEMM epilogue at 7 x 7 (Tp = 64), dvt_tune_set(18, 0) at
+    11 x 11 (64 x 64 tiles, unfused softmax backward, no fork), the inference ping-pong at 5 x 9 -- against what
+    tools/record_s2_parent_digests.py recorded from the parent commit of the change that gave that code one compiled copy
+    (tests/golden/s2_parent_digests.json).  A tensor recorded as a digest has the parent's bits (sha256); the loss, the
+    LayerNorm gradients and the tensors whose bits moved between the parent's own repeats ("observed" in the file) are held
+    to the recorded values within the recorder's tolerance (twice the parent's run-to-run spread, 4-ulp floor) -- the split
+    of tests/test_gpu_stage3_bf16.py."""
+    rec_mod, H = _recorder("record_s2_parent_digests"), _recorder("record_s3_golden")
+    with open(os.path.join(golden_dir, "s2_parent_digests.json")) as f:
+        rec = json.load(f)
+    got = rec_mod.step_tensors(torch, case)
+    want, varies = rec["cases"][case], rec["varies"][case]
+    assert set(got) == set(want) | set(varies) and not set(want) & set(varies)
+    assert all(H.is_atomic(k) or k in rec["observed"][case] for k in varies)
+    if case == "rows11x11":  # the default path: the k-contiguous weight gradients and pos_embed reproduce their bits
+        assert set(rec_mod.MUST_BE_STABLE[1]) <= set(want)
+    wrong = [k for k in want if H.digest(got[k]) != want[k]]
+    assert not wrong, wrong
+    for k, r in varies.items():
+        values, spread = H.unpack(torch, r)
+        err = float((got[k] - values).abs().max())
+        assert err <= H.tolerance(values, spread), (k, err, H.tolerance(values, spread))
 
 
 def test_adamw_vs_torch():
