@@ -18,6 +18,7 @@
 // dvt_grid_bwd gates both the gradient load and its clearing: one 32-bit word covers
 // 32 entries = 256 floats = exactly the 64 float4 one wave processes per iteration.
 #include "dvt_common.h"
+#include "dvt_tune.h"
 
 namespace {
 

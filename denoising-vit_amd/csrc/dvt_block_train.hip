@@ -10,13 +10,6 @@
 #include "dvt_row_dev.h"
 #include "../../include/dvt_parts.h"
 
-// dvt_gemm_f32.hip: the fp32 extractor's 128 x 128 x 32 exact-fp32 MFMA tile (x . w^T + b, shapes per dvt_linear_big_ok)
-int dvt_linear_fwd_big(const float* x, const float* w, const float* b, float* y, int m, int n, int k, hipStream_t s);
-bool dvt_linear_big_ok(int m, int n, int k);
-bool dvt_linear_wgrad_big_ok(int rows, int n, int k);
-int dvt_linear_wgrad_big(const float* dy, const float* x, float* dw, float* db, int rows, int n, int k, int accumulate,
-                         hipStream_t s);
-
 namespace {
 
 // ==========================================================================================================

@@ -222,6 +222,7 @@ __device__ __forceinline__ void dvt_shadow_store(const DvtShadowLayout& L, void*
   }
 }
 #endif
+extern int g_fit_sorted_grid;  // dvt_tune_set(7, v), defined and decoded in dvt_fit_fused.hip; dvt_fit.hip reads it
 bool dvt_fit_fused_ok(const DvtFitConfig* c);         // shapes fit AND the bf16-operand mode is selected
 bool dvt_fit_fused_shapes_ok(const DvtFitConfig* c);  // shapes only (workspace carving must not depend on the mode)
 int dvt_fit_rows_k(const DvtFitConfig* c, const DvtShadowLayout* L, int k, const DvtFusedFit* fits, bool phase2,
@@ -247,18 +248,6 @@ struct DvtProbeScope {
     if (idx >= 0) dvt_prof_end(probe, idx, gen, s, work);
   }
 };
-int dvt_vit_tune(int gemm_variant);
-// ... which asks the units of the ViT extractor in this order -- the forward (dvt_vit.hip), the fp32 extractor
-// (dvt_vit_f32.hip), attention (dvt_vit_attn.hip), GEMM (dvt_vit_gemm.hip) -- and the first that knows v answers: 0 (taken),
-// DVT_E_BADARG (its own, refused) or VIT_TUNE_NOT_MINE, which never leaves dvt_vit_tune.  Every unit keeps its knobs to itself.
-constexpr int VIT_TUNE_NOT_MINE = 1;
-int vit_forward_tune(int v);
-int vit_f32_tune(int v);
-int vit_attn_tune(int v);
-int vit_gemm_tune(int v);
-int dvt_grid_tune(int lds_level_max);
-int dvt_adam_tune(int zero_all);
-int dvt_s2_tune(int mask);
 
 // One linear-layer contraction for the grouped launch (dvt_gemm_f32.hip).
 struct DvtLinearOp {
@@ -274,7 +263,7 @@ struct DvtLinearOp {
   float* dx;
   int m, n, k, relu;
 };
-// General exact-fp32 GEMM (dvt_gemm_f32.hip), the building block of the stage-2 trainer.
+// General exact-fp32 GEMM (dvt_gemm_f32_glds.hip), the building block of the stage-2 trainer.
 //   layout 0: C[M][N] = A[M][K] . B[N][K]^T   (both k-contiguous: a forward linear layer)
 //   layout 1: C[M][N] = A[M][K] . B[K][N]     (a data gradient; N % 64 == 0)
 //   layout 2: C[M][N] = A[K][M]^T . B[K][N]   (a weight gradient; M % 64 == 0, N % 64 == 0)
@@ -299,6 +288,16 @@ struct DvtGemmEx {
   float oscale;
 };
 int dvt_gemm_f32_ex(const DvtGemmEx* g, hipStream_t s);
+// The 128 x 128 x 32 exact-fp32 tile (dvt_gemm_f32_big.hip) of the fp32 extractor and of stages 2 / 3.  dvt_linear_fwd_big:
+// y = x . w^T + b on that tile where dvt_linear_big_ok(m, n, k), else on a 64 x 64 tile; _epi (that tile only): epi 1 = exact-erf
+// GELU, epi 2 = y += gamma (.) (.); wgrad: dw[n][k] (+)= sum_r dy[r][n] x[r][k], db[n] += sum_r dy[r][n]
+bool dvt_linear_big_ok(int m, int n, int k);
+int dvt_linear_fwd_big(const float* x, const float* w, const float* b, float* y, int m, int n, int k, hipStream_t s);
+int dvt_linear_fwd_big_epi(const float* x, const float* w, const float* b, float* y, int m, int n, int k, int epi,
+                           const float* gamma, hipStream_t s);
+bool dvt_linear_wgrad_big_ok(int rows, int n, int k);
+int dvt_linear_wgrad_big(const float* dy, const float* x, float* dw, float* db, int rows, int n, int k, int accumulate,
+                         hipStream_t s);
 // bf16_operands: round operands to bf16 while staging (autocast semantics), fp32 otherwise
 int dvt_linear_group(const DvtLinearOp* ops, int n_ops, hipStream_t s, int bf16_operands = 0);
 int dvt_fit_prep(const DvtGridTable* tbl, const float* xy, const int32_t* ridx, const float* params,

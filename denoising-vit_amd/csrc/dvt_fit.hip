@@ -16,8 +16,10 @@
 
 #include "dvt_common.h"
 #include "dvt_grid_dev.h"
+#include "dvt_tune.h"
 
-extern int g_fit_sorted_grid;
+namespace {
+
 #ifdef DVT_LAB
 // developer library only, dvt_tune_set(15, mask): TIMING-ONLY ablation of the fused step -- bit 0 skips the row kernel, bit 1 the
 // backward kernel, bit 2 the Adam launch (results are wrong by construction; what each launch costs the PIPELINE: tools/r06)
@@ -34,6 +36,26 @@ int g_fit_lazy_exact = 0;
 int g_fit_lazy_refresh = 32;  // dvt_tune_set(9, n >= 2): steps between full sweeps of the lazy region
 
 int g_adam_pingpong = 1;  // dvt_tune_set(8, 0): always sweep forward (A/B timing)
+
+}  // namespace
+
+// This unit's share of dvt_tune_set (dvt_tune.h)
+int fit_tune(int key, int value) {
+  switch (key) {
+    case 8: g_adam_pingpong = value != 0; return 0;
+    case 9:
+      g_fit_lazy_adam = value != 0;
+      if (value >= 2) g_fit_lazy_refresh = value;
+      return 0;
+    case 10: g_fit_lazy_exact = value != 0; return 0;
+    case 11: g_fit_lazy_merge = value != 0; return 0;
+    case 12: g_fit_shadow_in_adam = value != 0; return 0;
+#ifdef DVT_LAB
+    case 15: g_fit_skip_mask = value & 7; return 0;
+#endif
+  }
+  return DVT_TUNE_NOT_MINE;
+}
 
 namespace {
 

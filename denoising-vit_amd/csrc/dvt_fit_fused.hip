@@ -32,15 +32,16 @@
 #include "dvt_common.h"
 #include "dvt_grid_dev.h"
 #include "dvt_loss_row.h"
+#include "dvt_tune.h"
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+namespace {
+
 int g_fit_rows32 = 1;  // dvt_tune_set(13, v), see launch_rows
 int g_fit_xcd_affinity = 1;  // dvt_tune_set(16, v): the row kernel's fit -> XCD map for 2 / 4 fits per launch (fit_rows_kernel) on / off
 int g_fit_small_wg = 0;  // dvt_tune_set(14, v): 1 = 4-wave fit_rows + 8-wave fit_backward workgroups (same arithmetic, same results)
-
-namespace {
 
 constexpr int FR0 = 16;  // rows per workgroup of the round-2 kernel = M of the MFMA; the kernel template takes FR = 16 or 32
 constexpr int FW8 = 8;   // waves per workgroup (template parameter FW of the kernels below: 8, or 4 = the small-footprint
@@ -761,10 +762,31 @@ int dvt_shadow_build_k(const DvtShadowLayout* L, int k, const float* const* para
   return 0;
 }
 
+namespace {
 int g_fit_fused_enable = 1;  // dvt_tune_set(6, 0): the unfused launch sequence (same results, A/B timing + parity)
-int g_fit_sorted_grid = 1;  // 0: the fused step scatters the grid gradient with atomics (round-2a path)
-
 int g_fit_fused_f32 = 1;  // dvt_tune_set(6, 2 / 3): fp32-operand fused step off / on (A/B against the layer-by-layer launches)
+}  // namespace
+int g_fit_sorted_grid = 1;  // dvt_tune_set(7, 0): the fused step scatters the grid gradient with atomics (round-2a path); dvt_fit.hip reads it too
+
+// This unit's share of dvt_tune_set (dvt_tune.h)
+int fit_fused_tune(int key, int value) {
+  switch (key) {
+    case 6:
+      if (value == 2 || value == 3)
+        g_fit_fused_f32 = value == 3;
+      else
+        g_fit_fused_enable = value != 0;
+      return 0;
+    case 7: g_fit_sorted_grid = value != 0; return 0;
+    case 13:
+      if (value < 0 || value > 2) return DVT_E_BADARG;
+      g_fit_rows32 = value;
+      return 0;
+    case 14: g_fit_small_wg = value != 0; return 0;
+    case 16: g_fit_xcd_affinity = value != 0; return 0;
+  }
+  return DVT_TUNE_NOT_MINE;
+}
 
 bool dvt_fit_fused_ok(const DvtFitConfig* c) {
   if (!g_fit_fused_enable || !c || !dvt_fit_fused_shapes_ok(c)) return false;

@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include "dvt_common.h"
 #include "dvt_block_train.h"
+#include "dvt_tune.h"
 #include "dvt_row_dev.h"
 #include "../../include/dvt_parts.h"
 #include "../../include/dvt_stage2.h"

@@ -13,6 +13,7 @@
 
 #include "../../include/dvt_vit.h"
 #include "dvt_common.h"
+#include "dvt_tune.h"
 // ---- tile order: blockIdx -> (m, n) tile, L2-aware (map_tile, map_tile_fast, map_tile_id, fd_make / fd_div); here because
 // the GEMM's argument block carries a TileOrder --------------------------------------------------------------------------
 #include "dvt_tile_map.h"
@@ -197,4 +198,4 @@ int vit_launch_cls_norm(const float* x, const DvtVitConfig* c, const float* norm
 // kernel without norm and without prefix rows (dim <= 1024)
 int vit_launch_rows_out(const float* x, float* out, int batch, int s_pad, int n_valid, int dim, hipStream_t s);
 // (the units' shares of dvt_tune_set(1, v) -- vit_forward_tune, vit_attn_tune, vit_gemm_tune and the fp32 extractor's
-// vit_f32_tune -- are declared next to dvt_vit_tune in dvt_common.h: dvt_vit_f32.hip does not include this header)
+// vit_f32_tune -- are declared next to dvt_vit_tune in dvt_tune.h: dvt_vit_f32.hip does not include this header)

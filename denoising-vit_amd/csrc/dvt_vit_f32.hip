@@ -15,16 +15,13 @@
 #include "../../include/dvt_vit.h"
 #include "dvt_common.h"
 #include "dvt_ln_row.h"
+#include "dvt_tune.h"
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef unsigned short bf16_t;
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 hw_bf16x2_t __attribute__((ext_vector_type(2)));
 
-int dvt_linear_fwd_big(const float* x, const float* w, const float* b, float* y, int m, int n, int k, hipStream_t s);
-bool dvt_linear_big_ok(int m, int n, int k);
-int dvt_linear_fwd_big_epi(const float* x, const float* w, const float* b, float* y, int m, int n, int k, int epi,
-                           const float* gamma, hipStream_t s);
 // bf16 GEMM kernels of dvt_vit_gemm.hip (fp32 accumulation) and the split-operand attention of dvt_vit_attn.hip, used by the bf16x3 mode below
 extern "C" int dvt_vit_gemm_f32out(const void* a, const void* w, const float* b, float* y, int m, int n, int k, void* stream);
 extern "C" int dvt_vit_gemm_residual(const void* a, const void* w, const float* b, const float* gamma, float* x, int m,

@@ -19,6 +19,9 @@ LAB_LIB_PATH = CSRC / "libdvt_hip_lab.so"  # developer build (-DDVT_LAB), see bu
 HIP_SOURCES = [
     "dvt_grid.hip",
     "dvt_gemm_f32.hip",
+    "dvt_gemm_f32_glds.hip",
+    "dvt_gemm_f32_big.hip",
+    "dvt_tune.hip",
     "dvt_loss.hip",
     "dvt_adam.hip",
     "dvt_fit.hip",
@@ -268,6 +271,9 @@ def build(force: bool = False, verbose: bool = False, lab: bool = False) -> Path
     epilogues in dvt_vit_epilogue.h) and dvt_vit_attn.hip (attention) -- that share dvt_vit_dev.h and compile side by side.
     The stage-2 and stage-3 trainers (dvt_stage2.hip, dvt_stage3.hip) share one compiled copy of their block code,
     dvt_block_train.hip (declared in dvt_block_train.h).
+    The exact-fp32 GEMM is three sources by tile family that share dvt_gemm_f32_dev.h: dvt_gemm_f32.hip (register-staged, the
+    stage-1 fit), dvt_gemm_f32_glds.hip (LDS-DMA ring, dvt_gemm_f32_ex) and dvt_gemm_f32_big.hip (128 x 128 x 32).  dvt_tune.hip
+    is dvt_tune_set alone: every unit decodes the keys of its own knobs (dvt_tune.h).
     lab=True builds the DEVELOPER library csrc/libdvt_hip_lab.so with -DDVT_LAB (superseded schedules, experiments and
     timing builds of csrc/lab/); nothing in dvt_amd loads it (tools/build_lab.py, tools/lab_*.py, tests/test_gpu_lab.py)."""
     from concurrent.futures import ThreadPoolExecutor

@@ -6,7 +6,7 @@ arguments and defaults, same attribute names (`neural_field` with `.params` /
 (`neural_field.params`, `mlp.0.weight`, `mlp.0.bias`, `mlp.2.weight`, `mlp.2.bias`), same
 `forward(coords[..., 2]) -> [..., feat_dim]`.  The tinycudann encoding (:25-39, :48) is
 replaced by the hand-written HIP kernels in csrc/dvt_grid.hip, the cuBLAS linears (:40-44,
-:49) by the f32-MFMA kernels in csrc/dvt_gemm_f32.hip; both are reached through the C ABI.
+:49) by the f32-MFMA kernels in csrc/dvt_gemm_f32.hip (body: dvt_gemm_f32_dev.h); both are reached through the C ABI.
 """
 from __future__ import annotations
 

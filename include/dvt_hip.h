@@ -305,9 +305,10 @@ int dvt_render_views(const float* img, int H, int W, const int32_t* boxes, float
  *         backward without a dP pass, bit 5 = a layer's weight gradient on a side stream beside its data gradient (0 = round 5's
  *         flow); results differ in summation order only (tests/test_gpu_stage2.py);
  * key 2 = grid backward: levels with more entries than `value` use global atomics (default 0 = all);
- * key 5 = fp32 GEMM k-depth of the register-staged kernel: 64 (default), 32, or 16 (10 KB LDS per
- *         workgroup, lets fit kernels co-reside with the ViT extractor's 136-144 KB workgroups);
- * key 4 = fp32 GEMM: 1 (default) use the 3-stage LDS-DMA kernel when eligible, 0 = register-staged only;
+ * key 5 = fp32 GEMM k-depth of the register-staged kernel: 32 (default: 17 KB LDS per workgroup), 16 (10 KB) -- both let fit
+ *         kernels co-reside with the ViT extractor's 136-144 KB workgroups --, or 64, which also lets the fit's layers take
+ *         the 3-stage LDS-DMA kernel of key 4;
+ * key 4 = fp32 GEMM: 1 (default) the fit uses the 3-stage LDS-DMA kernel when eligible and key 5 = 64, 0 = register-staged only;
  *         2 / 3 = LDS stages of the stage-2 GEMMs (2, default: two workgroups per CU);
  *         11 (default) / 10 = the fp32 extractor's linear layers on the 128 x 128 x 32 tile with fused GELU / residual
  *         epilogues (round 5) / on the 64 x 64 x 64 LDS-DMA kernel + separate row-local passes (results differ in summation

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-/* ---- dvt_gemm_f32.hip ------------------------------------------------------------------------------------ */
+/* ---- dvt_gemm_f32_glds.hip (dvt_parts_gemm_ex), dvt_gemm_f32_big.hip (dvt_parts_linear_big_epi) ----------------- */
 /* Mirror of the internal DvtGemmEx (csrc/dvt_common.h), field for field:
  *   layout 0: C[M][N] = A[M][K] . B[N][K]^T (+ bias[n]);  1: C = A[M][K] . B[K][N] (N % 64 == 0);
  *   layout 2: C = A[K][M]^T . B[K][N] (M % 64 == N % 64 == 0; colsum[m] += sum_k A[k][m]).

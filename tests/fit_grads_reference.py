@@ -16,7 +16,7 @@ small multiple of that distance; nothing in here ever sees a GPU result.
             (k-blocking, pairwise trees); that is systematically more accurate than a float32 accumulator, by sqrt(K / block),
             so it would be a yardstick for a precision the kernels do not claim.
             Four products per accumulator rounding is the MOST accurate thing that instruction could do.  The fp32 MFMA is
-            in fact an fmaf chain (csrc/dvt_gemm_f32.hip: "bitwise an fmaf chain"): one accumulator rounding per product,
+            in fact an fmaf chain (csrc/dvt_gemm_f32_dev.h: "bitwise an fmaf chain"): one accumulator rounding per product,
             four times as many, hence up to sqrt(4) = 2 x this comparator's rms error in a tensor whose error is all GEMM
             accumulation.  Replacing _mm_f32 by such a chain (fl32(acc + a_k b_k), the product exact in float64) moves the
             comparator's L2 error of the grid gradient at C = 1024 from 3.65e-07 to 6.97e-07; the kernels measure 7.13e-07.

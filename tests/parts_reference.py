@@ -72,7 +72,7 @@ def gemm_tol(absprod, K, splits=1, bias=None):
 
 
 def ex_splits(M, N, K, accumulate):
-    """k-split of dvt_gemm_f32_ex (unbatched): (splits, k-tiles of each split); restated from dvt_gemm_f32.hip."""
+    """k-split of dvt_gemm_f32_ex (unbatched): (splits, k-tiles of each split); restated from dvt_gemm_f32_glds.hip."""
     ktiles = K // 64
     if not accumulate:
         return 1, [ktiles]

@@ -381,6 +381,41 @@ def test_linear_big_epi_refusals(L):
         y.untouched(what)
 
 
+# ================================================== launches that cross the units of the fp32 GEMM (csrc/dvt_gemm_f32_dev.h)
+# dvt_linear_fwd_big -> the ring (dvt_gemm_f32_glds.hip) and -> the register-staged kernel (dvt_gemm_f32.hip) are crossed by
+# test_linear_big_fallbacks above, the batched small-k kernel beside the ring (body in the shared header), with and without the
+# softmax-backward epilogue and at both ring depths, by test_gemm_ex_batched[qk / dS].  The two below are the rest.
+def test_linear_big_tile_switched_off(L):
+    """dvt_tune_set(4, 10) -- decoded by the 128 x 128 unit -- sends the shape its tile would take (128 x 128 x 32) to another
+    unit: k = 32 is no whole 64-tile, so to the register-staged kernel.  Tolerance: test_linear_big_fallbacks' (big_epi_case)."""
+    with Knob(L, 4, 10, 11):
+        big_epi_case(L, 128, 128, 32, 0, True, "linear_big.fallback")
+
+
+def test_fit_linear_on_the_ring(L):
+    """dvt_tune_set(5, 64): dvt_linear_fwd / dvt_linear_bwd (the fit's unit) launch the ring of dvt_gemm_f32_glds.hip through
+    its launcher, at m = n = k = 64: the smallest shape the ring takes in all three layouts (forward, dgrad with the ReLU mask,
+    atomically accumulated wgrad with the bias gradient).  Against float64 products of the same inputs, with the bounds of
+    tests/test_gpu_kernels.py::test_linear_fwd_bwd_vs_torch: 2e-6 of the largest element forward and dgrad, 2e-5 wgrad and bias."""
+    g = pr.gen(pr.seed_of("fit_ring", 64))
+    x, w, b, dy, mask = pr.randn(g, 64, 64), pr.randn(g, 64, 64) / 8, pr.randn(g, 64), pr.randn(g, 64, 64), pr.randn(g, 64, 64)
+    X, W, B_, DY, MK = dev(x), dev(w), dev(b), dev(dy), dev(mask)
+    y, dx = Buf((64, 64)), Buf((64, 64))
+    dw, db = Buf((64, 64), fill=torch.zeros(64, 64)), Buf((64,), fill=torch.zeros(64))
+    with Knob(L, 5, 64, 32):
+        rc_f = L.dvt_linear_fwd(X.data_ptr(), W.data_ptr(), B_.data_ptr(), y.ptr(), 64, 64, 64, 1, _s())
+        rc_b = L.dvt_linear_bwd(DY.data_ptr(), X.data_ptr(), W.data_ptr(), dw.ptr(), db.ptr(), dx.ptr(), MK.data_ptr(), 64, 64, 64, _s())
+        torch.cuda.synchronize()
+    assert rc_f == 0 and rc_b == 0
+    x, w, b, dy = x.double(), w.double(), b.double(), dy.double()
+    want = {"y": (x @ w.t() + b).relu(), "dx": (dy @ w) * (mask > 0), "dw": dy.t() @ x, "db": dy.sum(0)}
+    for name, buf, bound in (("y", y, 2e-6), ("dx", dx, 2e-6), ("dw", dw, 2e-5), ("db", db, 2e-5)):
+        buf.check(f"fit on the ring {name}")
+        err = float((buf.out.double().cpu().reshape(want[name].shape) - want[name]).abs().max() / want[name].abs().max())
+        print(f"fit on the ring {name}: relative error {err:.3g}")
+        assert err < bound, name
+
+
 # =================================================================================== dvt_parts_lin_fwd / dvt_parts_lin_bwd
 def big_wgrad_taken(mask, R, n, k):
     return bool(mask & 4) and R % 32 == 0 and n % 128 == 0 and k % 128 == 0

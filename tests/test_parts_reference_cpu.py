@@ -174,7 +174,7 @@ def test_attention_references():
 
 
 def test_gemm_struct_mirror_size():
-    """DvtPartsGemmEx is padded explicitly; dvt_gemm_f32.hip asserts the same 160 bytes at compile time."""
+    """DvtPartsGemmEx is padded explicitly; dvt_gemm_f32_glds.hip asserts the same 160 bytes at compile time."""
     import ctypes
     from dvt_amd._lib import PartsGemmEx
     assert ctypes.sizeof(PartsGemmEx) == 160 and PartsGemmEx.oscale.offset == 152 and PartsGemmEx.sA0.offset == 88
