@@ -1,13 +1,10 @@
-// The transformer block's exact-fp32 training code that the stage-2 step (dvt_stage2.hip) and the stage-3 step
-// (dvt_stage3.hip) both run, compiled once in dvt_block_train.hip.  Ordinary C++ functions, not part of the C ABI.
+// The trained transformer block of the stage-2 step (dvt_stage2.hip) and of the stage-3 step (dvt_stage3.hip), compiled once
+// in dvt_block_train.hip: its pieces (linear layers, LayerNorm with the residual add in front and its backward, LayerScale
+// backward, GELU, attention, loss rows, the side stream), the block's forward and backward launch sequences block_fwd /
+// block_bwd at the end of this header, and the carving of a block's workspace.  Both steps keep what surrounds the blocks: input
+// assembly, the norm behind each block, loss and optimizer.  Ordinary C++ functions, not part of the C ABI.
 #pragma once
 #include "dvt_common.h"
-
-#define S2_TRY(x)               \
-  do {                          \
-    const int rc__ = (x);       \
-    if (rc__ != 0) return rc__; \
-  } while (0)
 
 // dvt_stage2.hip: the process's A/B switches (dvt_tune_set(18, mask), DVT_S2_* in the environment) and the two softmax
 // passes over a [rows][Tp] score matrix that the unfused attention branches run
@@ -66,3 +63,72 @@ int block_attn_fwd(const AttnDims& d, const float* qkv, float* P, float* ao, flo
 // (fuse_softmax_bwd alone), or the plain product and s2_softmax_bwd over it
 int block_attn_bwd(const AttnDims& d, const float* qkv, const float* P, const float* ao, const float* dao, float* dqkv,
                    float* dP, float* rowdot, float scale, bool rows_kernel, bool fuse_softmax_bwd, hipStream_t s);
+
+// Residual add fused with the LayerNorm behind it, one wave per row: sum_out (may be null) = a + b, xn = LayerNorm(sum),
+// per-row mean / rstd kept; rows t >= T of an image's Tp: all zero.  add_ln: a packed [batch, T, C] or padded [R, C], b null,
+// pos_embed [T, C] or padded.  ls_add_ln: sum = a + ls (.) f, or a alone with ls null.  resid_ln: the block's residual
+// add, LayerScale or none
+int add_ln(int C, const float* a, int a_packed, const float* b, int b_is_pos, float* sum_out, const float* gamma,
+           const float* beta, float* xn, float* mean, float* rstd, int T, int Tp, int R, float eps, hipStream_t s);
+int ls_add_ln(int C, const float* a, const float* f, const float* ls, float* sum_out, const float* gamma, const float* beta,
+              float* xn, float* mean, float* rstd, int T, int Tp, int R, float eps, hipStream_t s);
+inline int resid_ln(int C, const float* a, const float* f, const float* ls, float* sum_out, const float* gamma,
+                    const float* beta, float* xn, float* mean, float* rstd, int T, int Tp, int R, float eps, hipStream_t s) {
+  return ls ? ls_add_ln(C, a, f, ls, sum_out, gamma, beta, xn, mean, rstd, T, Tp, R, eps, s)
+            : add_ln(C, a, 0, f, 0, sum_out, gamma, beta, xn, mean, rstd, T, Tp, R, eps, s);
+}
+
+// ---- the block ----
+// A block's tensors inside `params` (F = const float) or `grads` (F = float).  ls1 == ls2 == nullptr: no LayerScale (stage 2)
+template <typename F>
+struct BlockTensors {
+  F *n1w, *n1b, *qkvw, *qkvb, *projw, *projb, *ls1, *n2w, *n2b, *fc1w, *fc1b, *fc2w, *fc2b, *ls2;
+};
+// base + off[i] in the order above; off holds 14 entries with_ls, else the 12 without ls1 / ls2
+template <typename F>
+BlockTensors<F> block_tensors(F* base, const int64_t* off, bool with_ls) {
+  auto at = [&] { return base + *off++; };
+  BlockTensors<F> t{};
+  t.n1w = at(), t.n1b = at(), t.qkvw = at(), t.qkvb = at(), t.projw = at(), t.projb = at();
+  if (with_ls) t.ls1 = at();
+  t.n2w = at(), t.n2b = at(), t.fc1w = at(), t.fc1b = at(), t.fc2w = at(), t.fc2b = at();
+  if (with_ls) t.ls2 = at();
+  return t;
+}
+struct BlockActs {  // what the forward writes and the backward reads
+  float *xin, *xn1, *mean1, *rstd1, *qkv, *P, *ao, *f1, *x1, *xn2, *mean2, *rstd2, *h, *a, *f2;
+};
+struct BlockScratch {  // one set for all blocks: the backward's gradients in flight
+  float *d0, *d1, *d2, *dh, *dqkv, *dP, *acc, *wT, *rowdot;
+};
+struct BlockBf16 {  // stage 3's gemm_mode 1: the qkv / proj / fc1 / fc2 weights as bf16, [n, k] and transposed [k, n], and the
+  uint16_t *w[4], *wt[4], *abf;  // scratch the A operand of the GEMM about to run is rounded into
+};
+struct BlockDims {
+  AttnDims ad;
+  int F;  // mlp_dim
+  float eps;
+};
+// Buffer contract: the caller has written xin and xn1 / mean1 / rstd1 = norm1(xin); block_fwd fills the rest of k and ends with
+// f2 = fc2(gelu(fc1(xn2))) written and NOT added: f1 and f2 are the caller's (a block's own, or one buffer for both where no
+// LayerScale gradient reads them), and the residual add of f2 with the norm behind it is the caller's resid_ln.  block_bwd
+// takes d0 = d(block output), leaves d0 = d xin and uses d1, d2, dh, dqkv, dP, rowdot, wT as scratch.
+// mp null: exact fp32; else forward and data-gradient GEMMs on bf16 operands, weight gradients exact all the same.
+int block_fwd(const BlockDims& d, const BlockTensors<const float>& p, const BlockActs& k, const BlockBf16* mp, bool rows_kernel,
+              hipStream_t s);
+int block_bwd(const BlockDims& d, const BlockTensors<const float>& p, const BlockTensors<float>& g, const BlockActs& k,
+              const BlockScratch& w, const BlockBf16* mp, bool rows_kernel, bool fuse_softmax_bwd, hipStream_t s);
+
+// Workspace carving of both steps: take() is the next piece of `base` (null: sizes only) in whole 256-byte units
+struct Carver {
+  char* base;
+  int64_t o = 0;
+  float* take(int64_t floats) {
+    float* p = base ? reinterpret_cast<float*>(base + o) : nullptr;
+    o += (floats * 4 + 255) / 256 * 256;
+    return p;
+  }
+};
+// R rows, C columns, F mlp columns, PP floats of P.  own_f: f1 behind ao and f2 at the end, else both left null
+void carve_block_acts(Carver& cv, BlockActs* k, int64_t R, int64_t C, int64_t F, int64_t PP, bool own_f);
+void carve_block_scratch(Carver& cv, BlockScratch* w, int64_t R, int64_t C, int64_t F, int64_t PP, int64_t rowdot_floats);

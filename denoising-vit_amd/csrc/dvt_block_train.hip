@@ -1,16 +1,165 @@
-// The transformer block's exact-fp32 training pieces that the stage-2 step (dvt_stage2.hip) and the stage-3 step
-// (dvt_stage3.hip) both run (dvt_block_train.h): LayerNorm backward, GELU, the fused attention-row kernels, the loss rows,
-// the linear layers' forward / backward on the 128 x 128 x 32 exact-fp32 tile, the batched attention products with the
-// attention forward / backward launch sequences around them, and the side stream those sequences fork onto.  One compiled
-// copy: what tests/test_gpu_parts.py drives through the dvt_parts_* forwarders at the end of this file is exactly what both
-// trainers launch.  The A/B switches are the process's, defined in dvt_stage2.hip.
+// The trained transformer block that the stage-2 step (dvt_stage2.hip) and the stage-3 step (dvt_stage3.hip) both run
+// (dvt_block_train.h).  Its pieces: the residual add fused with the LayerNorm behind it (plain and LayerScale), LayerNorm and
+// LayerScale backward, GELU, the fused attention-row kernels, the loss rows, the linear layers' forward / backward on the
+// 128 x 128 x 32 exact-fp32 tile (or, stage 3's opt-in, on the bf16 GEMM), the batched attention products with the attention
+// forward / backward launch sequences around them, and the side stream those sequences fork onto.  Then the block itself,
+// block_fwd / block_bwd, and the carving of its workspace.  One compiled copy: what tests/test_gpu_parts.py drives through the
+// dvt_parts_* forwarders at the end of this file is exactly what both trainers launch.  The A/B switches are the process's,
+// defined in dvt_stage2.hip.
 #include <map>
 #include <mutex>
 #include "dvt_block_train.h"
 #include "dvt_row_dev.h"
 #include "../../include/dvt_parts.h"
+#include "../../include/dvt_stage3.h"
 
 namespace {
+
+// ==========================================================================================================
+// (a [+ b]) -> sum, LayerNorm(sum) -> xn, per-row mean / rstd.  One wave per row.
+//   a: packed [batch, T, C] (a_packed) or padded [R, C];  b: nullptr, pos_embed [T, C] (b_is_pos) or padded [R, C]
+// Rows t >= T: sum = xn = 0, mean = rstd = 0.
+// online_denoiser.py:88-89 (x + pos_embed), Block: x + attn(norm1(x)), x + mlp(norm2(x)).
+// ==========================================================================================================
+template <int C>
+__global__ __launch_bounds__(256) void s2_add_ln_kernel(const float* __restrict__ a, int a_packed,
+                                                        const float* __restrict__ b, int b_is_pos,
+                                                        float* __restrict__ sum_out, const float* __restrict__ gamma,
+                                                        const float* __restrict__ beta, float* __restrict__ xn,
+                                                        float* __restrict__ mean, float* __restrict__ rstd, int T,
+                                                        int Tp, int R, float eps) {
+  const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= R) return;
+  const int img = r / Tp, t = r - img * Tp;
+  Row<C> x;
+  if (t >= T) {
+    x.zero();
+    if (sum_out) x.store(sum_out + (size_t)r * C, lane);
+    x.store(xn + (size_t)r * C, lane);
+    if (lane == 0) {
+      mean[r] = 0.f;
+      rstd[r] = 0.f;
+    }
+    return;
+  }
+  x.load(a_packed ? a + ((size_t)img * T + t) * C : a + (size_t)r * C, lane);
+  if (b) {
+    Row<C> y;
+    y.load(b_is_pos ? b + (size_t)t * C : b + (size_t)r * C, lane);
+    ROW_FOR(j, Row<C>::NJ) x.v[j] = f4_add(x.v[j], y.v[j]);
+  }
+  if (sum_out) x.store(sum_out + (size_t)r * C, lane);
+  const float mu = x.sum() * (1.0f / C);
+  Row<C> d;
+  float ss = 0.f;
+  ROW_FOR(j, Row<C>::NJ) {
+    const int i = lane + 64 * j;
+    d.v[j] = (i < C / 4) ? f4_sub(x.v[j], make_float4(mu, mu, mu, mu)) : make_float4(0.f, 0.f, 0.f, 0.f);
+    ss += f4_dot(d.v[j], d.v[j]);
+  }
+  const float var = wave_sum(ss) * (1.0f / C);
+  const float rs = 1.0f / sqrtf(var + eps);
+  Row<C> g, be;
+  g.load(gamma, lane);
+  be.load(beta, lane);
+  ROW_FOR(j, Row<C>::NJ) d.v[j] = f4_add(f4_mul(f4_scale(d.v[j], rs), g.v[j]), be.v[j]);
+  d.store(xn + (size_t)r * C, lane);
+  if (lane == 0) {
+    mean[r] = mu;
+    rstd[r] = rs;
+  }
+}
+
+// ==========================================================================================================
+// LayerScale residual add fused with the LayerNorm behind it, one wave per row (timm Block: x = x + ls(f(norm(x))), then the
+// next block's norm1 or the final norm):  sum = a + ls (.) f,  xn = LayerNorm(sum) * gamma + beta, per-row mean / rstd kept.
+// ls == nullptr: sum = a (the first block's norm1).  Rows t >= T: sum = xn = 0, mean = rstd = 0.  LayerNorm arithmetic as
+// s2_add_ln_kernel (two passes, 1 / sqrt(var + eps)).
+// ==========================================================================================================
+template <int C>
+__global__ __launch_bounds__(256) void s3_ls_add_ln_kernel(const float* __restrict__ a, const float* __restrict__ f,
+                                                           const float* __restrict__ ls, float* __restrict__ sum_out,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           float* __restrict__ xn, float* __restrict__ mean,
+                                                           float* __restrict__ rstd, int T, int Tp, int R, float eps) {
+  const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= R) return;
+  const int t = r % Tp;
+  Row<C> x;
+  if (t >= T) {
+    x.zero();
+    if (sum_out) x.store(sum_out + (size_t)r * C, lane);
+    x.store(xn + (size_t)r * C, lane);
+    if (lane == 0) {
+      mean[r] = 0.f;
+      rstd[r] = 0.f;
+    }
+    return;
+  }
+  x.load(a + (size_t)r * C, lane);
+  if (ls) {
+    Row<C> y, g;
+    y.load(f + (size_t)r * C, lane);
+    g.load(ls, lane);
+    ROW_FOR(j, Row<C>::NJ) x.v[j] = f4_add(x.v[j], f4_mul(g.v[j], y.v[j]));
+  }
+  if (sum_out) x.store(sum_out + (size_t)r * C, lane);
+  const float mu = x.sum() * (1.0f / C);
+  Row<C> d;
+  float ss = 0.f;
+  ROW_FOR(j, Row<C>::NJ) {
+    const int i = lane + 64 * j;
+    d.v[j] = (i < C / 4) ? f4_sub(x.v[j], make_float4(mu, mu, mu, mu)) : make_float4(0.f, 0.f, 0.f, 0.f);
+    ss += f4_dot(d.v[j], d.v[j]);
+  }
+  const float var = wave_sum(ss) * (1.0f / C);
+  const float rs = 1.0f / sqrtf(var + eps);
+  Row<C> g, be;
+  g.load(gamma, lane);
+  be.load(beta, lane);
+  ROW_FOR(j, Row<C>::NJ) d.v[j] = f4_add(f4_mul(f4_scale(d.v[j], rs), g.v[j]), be.v[j]);
+  d.store(xn + (size_t)r * C, lane);
+  if (lane == 0) {
+    mean[r] = mu;
+    rstd[r] = rs;
+  }
+}
+
+// ==========================================================================================================
+// LayerScale backward: y = x + ls (.) f  ->  df = ls (.) dy,  dls += sum_rows f (.) dy  (dx = dy is the caller's residual).
+// A 256-thread block walks 32 rows (8 per wave), reduces the 4 waves through LDS and issues one atomic per column, as
+// s2_ln_bwd_kernel does.
+// ==========================================================================================================
+template <int C>
+__global__ __launch_bounds__(256) void s3_ls_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ f,
+                                                        const float* __restrict__ ls, float* __restrict__ df,
+                                                        float* __restrict__ dls, int R) {
+  constexpr int NJ = Row<C>::NJ;
+  __shared__ float red[4][C];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  Row<C> g, acc;
+  g.load(ls, lane);
+  acc.zero();
+  const int r0 = blockIdx.x * 32 + wave * 8;
+  for (int i = 0; i < 8; ++i) {
+    const int r = r0 + i;
+    if (r >= R) break;
+    Row<C> d, fv;
+    d.load(dy + (size_t)r * C, lane);
+    fv.load(f + (size_t)r * C, lane);
+    ROW_FOR(j, NJ) {
+      acc.v[j] = f4_add(acc.v[j], f4_mul(fv.v[j], d.v[j]));
+      d.v[j] = f4_mul(g.v[j], d.v[j]);
+    }
+    d.store(df + (size_t)r * C, lane);
+  }
+  ROW_FOR(j, NJ) {
+    const int idx = lane + 64 * j;
+    if (idx < C / 4) *reinterpret_cast<float4*>(&red[wave][4 * idx]) = acc.v[j];
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += 256) atomic_add_f32(dls + c, (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]));
+}
 
 // ==========================================================================================================
 // LayerNorm backward fused with the residual-path gradient:
@@ -468,8 +617,8 @@ int loss_rows(bool add, int C, const float* a, const float* b, const float* targ
   const float inv_el = 1.0f / (N * C), inv_tok = 1.0f / N;
   const hipError_t e = hipMemsetAsync(acc, 0, 64 * sizeof(float), s);
   if (e != hipSuccess) return (int)e;
-  if (add) S2_TRY(loss_rows_t<true>(C, a, b, target, out, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok, s));
-  else S2_TRY(loss_rows_t<false>(C, a, b, target, out, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok, s));
+  if (add) DVT_TRY(loss_rows_t<true>(C, a, b, target, out, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok, s));
+  else DVT_TRY(loss_rows_t<false>(C, a, b, target, out, dout, acc, n_prefix, T, Tp, R, inv_el, inv_tok, s));
   hipLaunchKernelGGL(s2_loss_finish_kernel, dim3(1), dim3(1), 0, s, (const float*)acc, loss_out, inv_el, inv_tok);
   DVT_CHECK_LAUNCH();
   return 0;
@@ -522,10 +671,10 @@ int lin_bwd(const float* dy, const float* x, const float* w, float* dx, float* d
   // full), so the weight gradient goes to a side stream and the two fill each other's tails; joined before this returns (the
   // caller's next kernels overwrite dy / x).
   BlockFork f(s, dx != nullptr);
-  S2_TRY(f.fork());
+  DVT_TRY(f.fork());
   const hipStream_t sw = f.side();
   if (g_s2_big_wgrad && dvt_linear_wgrad_big_ok(R, n, k)) {  // round 6: the weight gradient on the 128 x 128 tile too
-    S2_TRY(dvt_linear_wgrad_big(dy, x, dw, db, R, n, k, 1, sw));
+    DVT_TRY(dvt_linear_wgrad_big(dy, x, dw, db, R, n, k, 1, sw));
   } else {
     DvtGemmEx g{};
     g.layout = 2;
@@ -534,20 +683,20 @@ int lin_bwd(const float* dy, const float* x, const float* w, float* dx, float* d
     g.lda = n; g.ldb = k; g.ldc = k;
     g.colsum = db;
     g.accumulate = 1;
-    S2_TRY(dvt_gemm_f32_ex(&g, sw));
+    DVT_TRY(dvt_gemm_f32_ex(&g, sw));
   }
   if (!dx) return 0;
   if (wT && g_s2_big_bwd && n % 32 == 0 && k % 32 == 0 && dvt_linear_big_ok(R, k, n)) {
     hipLaunchKernelGGL(s2_transpose_kernel, dim3(k / 32, n / 32), dim3(256), 0, s, w, wT, n, k);
     DVT_CHECK_LAUNCH();
-    S2_TRY(dvt_linear_fwd_big(dy, wT, nullptr, dx, R, k, n, s));
+    DVT_TRY(dvt_linear_fwd_big(dy, wT, nullptr, dx, R, k, n, s));
   } else {
     DvtGemmEx d{};
     d.layout = 1;
     d.A = dy; d.B = w; d.C = dx;
     d.M = R; d.N = k; d.K = n;
     d.lda = n; d.ldb = k; d.ldc = k;
-    S2_TRY(dvt_gemm_f32_ex(&d, s));
+    DVT_TRY(dvt_gemm_f32_ex(&d, s));
   }
   return f.join();
 }
@@ -557,11 +706,11 @@ int block_attn_fwd(const AttnDims& d, const float* qkv, float* P, float* ao, flo
   const AttnStrides st(d);
   DvtGemmEx g{};
   if (rows_kernel) {  // round 6: q k^T and the softmax in one kernel, P written once
-    S2_TRY(attn_rows(0, qkv, 3 * C, qkv + C, 3 * C, nullptr, nullptr, P, d.batch, d.heads, d.T, Tp, scale, s));
+    DVT_TRY(attn_rows(0, qkv, 3 * C, qkv + C, 3 * C, nullptr, nullptr, P, d.batch, d.heads, d.T, Tp, scale, s));
   } else {
     g = attn_gemm(d, 0, qkv, 3 * C, st.qs0, st.qs1, qkv + C, 3 * C, st.qs0, st.qs1, P, Tp, st.ps0, st.ps1, Tp, Tp, 64);
-    S2_TRY(dvt_gemm_f32_ex(&g, s));
-    S2_TRY(s2_softmax(P, d.T, Tp, (int64_t)d.batch * d.heads * Tp, scale, s));
+    DVT_TRY(dvt_gemm_f32_ex(&g, s));
+    DVT_TRY(s2_softmax(P, d.T, Tp, (int64_t)d.batch * d.heads * Tp, scale, s));
   }
   g = attn_gemm(d, 1, P, Tp, st.ps0, st.ps1, qkv + 2 * C, 3 * C, st.qs0, st.qs1, ao, C, st.os0, st.os1, Tp, 64, Tp);
   return dvt_gemm_f32_ex(&g, s);
@@ -575,33 +724,163 @@ int block_attn_bwd(const AttnDims& d, const float* qkv, const float* P, const fl
   // gradients in lin_bwd); dq and dk, two products of the same dS, likewise.  Joined before the caller's lin_bwd reads dqkv.
   BlockFork f(s);
   const hipStream_t sv = f.side();
-  S2_TRY(f.fork());
+  DVT_TRY(f.fork());
   DvtGemmEx g = attn_gemm(d, 2, P, Tp, st.ps0, st.ps1, dao, C, st.os0, st.os1, dqkv + 2 * C, 3 * C, st.qs0, st.qs1, Tp, 64, Tp);
-  S2_TRY(dvt_gemm_f32_ex(&g, sv));
+  DVT_TRY(dvt_gemm_f32_ex(&g, sv));
   // dP = dao v^T, and the softmax backward dS = scale P (.) (dP - rowsum(dP (.) P)).  Round 6: rowsum(dP (.) P) = dao . ao per
   // (image, head, query) comes from the two [R][C] tensors (s2_rowdot_kernel) and the backward is the EPILOGUE of the dP
   // product -- dP is never written, P read once (before: 3 GB written + 9 GB read + 3 GB written by s2_softmax_bwd_kernel)
   g = attn_gemm(d, 0, dao, C, st.os0, st.os1, qkv + 2 * C, 3 * C, st.qs0, st.qs1, dP, Tp, st.ps0, st.ps1, Tp, Tp, 64);
   if (fuse_softmax_bwd && rows_kernel) {
-    S2_TRY(rowdot(dao, ao, rowdot_buf, R, Tp, C, s));
-    S2_TRY(attn_rows(1, dao, C, qkv + 2 * C, 3 * C, P, rowdot_buf, dP, d.batch, d.heads, d.T, Tp, scale, s));
+    DVT_TRY(rowdot(dao, ao, rowdot_buf, R, Tp, C, s));
+    DVT_TRY(attn_rows(1, dao, C, qkv + 2 * C, 3 * C, P, rowdot_buf, dP, d.batch, d.heads, d.T, Tp, scale, s));
   } else if (fuse_softmax_bwd) {
-    S2_TRY(rowdot(dao, ao, rowdot_buf, R, Tp, C, s));
+    DVT_TRY(rowdot(dao, ao, rowdot_buf, R, Tp, C, s));
     g.smul = P;
     g.rowsub = rowdot_buf;
     g.oscale = scale;
-    S2_TRY(dvt_gemm_f32_ex(&g, s));
+    DVT_TRY(dvt_gemm_f32_ex(&g, s));
   } else {
-    S2_TRY(dvt_gemm_f32_ex(&g, s));
-    S2_TRY(s2_softmax_bwd(P, dP, Tp, (int64_t)d.batch * d.heads * Tp, scale, s));
+    DVT_TRY(dvt_gemm_f32_ex(&g, s));
+    DVT_TRY(s2_softmax_bwd(P, dP, Tp, (int64_t)d.batch * d.heads * Tp, scale, s));
   }
   // dq = dS k (main stream),  dk = dS^T q (side stream: behind dV there, and behind dS here)
-  S2_TRY(f.fork());
+  DVT_TRY(f.fork());
   g = attn_gemm(d, 1, dP, Tp, st.ps0, st.ps1, qkv + C, 3 * C, st.qs0, st.qs1, dqkv, 3 * C, st.qs0, st.qs1, Tp, 64, Tp);
-  S2_TRY(dvt_gemm_f32_ex(&g, s));
+  DVT_TRY(dvt_gemm_f32_ex(&g, s));
   g = attn_gemm(d, 2, dP, Tp, st.ps0, st.ps1, qkv, 3 * C, st.qs0, st.qs1, dqkv + C, 3 * C, st.qs0, st.qs1, Tp, 64, Tp);
-  S2_TRY(dvt_gemm_f32_ex(&g, sv));
+  DVT_TRY(dvt_gemm_f32_ex(&g, sv));
   return f.join();
+}
+
+int add_ln(int C, const float* a, int a_packed, const float* b, int b_is_pos, float* sum_out, const float* g,
+           const float* be, float* xn, float* mean, float* rstd, int T, int Tp, int R, float eps, hipStream_t s) {
+  switch (C) {
+    case 384: return launch_rows(s2_add_ln_kernel<384>, R, s, a, a_packed, b, b_is_pos, sum_out, g, be, xn, mean, rstd, T, Tp, R, eps);
+    case 768: return launch_rows(s2_add_ln_kernel<768>, R, s, a, a_packed, b, b_is_pos, sum_out, g, be, xn, mean, rstd, T, Tp, R, eps);
+    default: return launch_rows(s2_add_ln_kernel<1024>, R, s, a, a_packed, b, b_is_pos, sum_out, g, be, xn, mean, rstd, T, Tp, R, eps);
+  }
+}
+
+int ls_add_ln(int C, const float* a, const float* f, const float* ls, float* sum_out, const float* g, const float* be,
+              float* xn, float* mean, float* rstd, int T, int Tp, int R, float eps, hipStream_t s) {
+  switch (C) {
+    case 384: return launch_rows(s3_ls_add_ln_kernel<384>, R, s, a, f, ls, sum_out, g, be, xn, mean, rstd, T, Tp, R, eps);
+    case 768: return launch_rows(s3_ls_add_ln_kernel<768>, R, s, a, f, ls, sum_out, g, be, xn, mean, rstd, T, Tp, R, eps);
+    default: return launch_rows(s3_ls_add_ln_kernel<1024>, R, s, a, f, ls, sum_out, g, be, xn, mean, rstd, T, Tp, R, eps);
+  }
+}
+
+static int ls_bwd(int C, const float* dy, const float* f, const float* ls, float* df, float* dls, int R, hipStream_t s) {
+  const dim3 grid(dvt_cdiv(R, 32)), blk(256);
+  switch (C) {
+    case 384: hipLaunchKernelGGL(s3_ls_bwd_kernel<384>, grid, blk, 0, s, dy, f, ls, df, dls, R); break;
+    case 768: hipLaunchKernelGGL(s3_ls_bwd_kernel<768>, grid, blk, 0, s, dy, f, ls, df, dls, R); break;
+    default: hipLaunchKernelGGL(s3_ls_bwd_kernel<1024>, grid, blk, 0, s, dy, f, ls, df, dls, R); break;
+  }
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- a linear layer of the block, exact fp32 (mp null) or, stage 3's gemm_mode 1, its forward and data gradient on the
+// extractor's bf16 GEMM (dvt_vit_gemm.hip, EPI_F32: bf16 operands, fp32 accumulation, fp32 output; m % 128 == n % 128 ==
+// k % 64 == 0, which stage 3's check_cfg guarantees for every layer of the block: R = batch s_pad with s_pad % 128 == 0, dim in
+// {384, 768, 1024}, mlp_dim % 128 == 0).  The A operand is rounded into `abf` right here; the weights (j: qkv, proj, fc1, fc2)
+// were rounded by the caller. ----
+static bool mp_shape_ok(int R, int n, int k) { return R > 0 && R % 128 == 0 && n % 128 == 0 && k % 64 == 0; }
+
+// y[R][n] = x[R][k] . w[n][k]^T + b
+static int blk_lin_fwd(const BlockBf16* mp, int j, const float* x, const float* w, const float* b, float* y, int R, int n, int k,
+                       hipStream_t s) {
+  if (!mp) return lin_fwd(x, w, b, y, R, n, k, s);
+  if (!mp_shape_ok(R, n, k)) return DVT_E_BADARG;
+  DVT_TRY(dvt_s3_cast_bf16(x, mp->abf, R, k, s));
+  return dvt_vit_gemm_f32out(mp->abf, mp->w[j], b, y, R, n, k, s);
+}
+
+// dx[R][k] = dy[R][n] . w[n][k];  dw[n][k] += dy^T . x and db[n] += colsum(dy), with mp too in exact fp32 from the UNROUNDED dy
+// and x, on lin_bwd's side stream beside the data gradient as in the fp32 mode
+static int blk_lin_bwd(const BlockBf16* mp, int j, const float* dy, const float* x, const float* w, float* dx, float* dw, float* db,
+                       int R, int n, int k, hipStream_t s, float* wT) {
+  if (!mp) return lin_bwd(dy, x, w, dx, dw, db, R, n, k, s, wT);
+  if (!mp_shape_ok(R, k, n)) return DVT_E_BADARG;
+  BlockFork f(s);
+  DVT_TRY(f.fork());
+  DVT_TRY(lin_bwd(dy, x, nullptr, nullptr, dw, db, R, n, k, f.side()));  // no dx: the weight and bias gradients alone, beside
+  DVT_TRY(dvt_s3_cast_bf16(dy, mp->abf, R, n, s));
+  DVT_TRY(dvt_vit_gemm_f32out(mp->abf, mp->wt[j], nullptr, dx, R, k, n, s));
+  return f.join();
+}
+
+// ---- the block (dvt_block_train.h): x1 = xin + [ls1 (.)] proj(attn(norm1 xin)), out = x1 + [ls2 (.)] fc2(gelu(fc1(norm2 x1))) ----
+static const float kAttnScale = 0.125f;  // head_dim^-0.5
+enum { WQKV = 0, WPROJ, WFC1, WFC2 };
+
+int block_fwd(const BlockDims& d, const BlockTensors<const float>& p, const BlockActs& k, const BlockBf16* mp, bool rows_kernel,
+              hipStream_t s) {
+  const int C = d.ad.C, F = d.F, T = d.ad.T, Tp = d.ad.Tp, R = d.ad.batch * Tp;
+  DVT_TRY(blk_lin_fwd(mp, WQKV, k.xn1, p.qkvw, p.qkvb, k.qkv, R, 3 * C, C, s));
+  DVT_TRY(block_attn_fwd(d.ad, k.qkv, k.P, k.ao, kAttnScale, rows_kernel, s));  // P = softmax(scale q k^T), ao = P v
+  DVT_TRY(blk_lin_fwd(mp, WPROJ, k.ao, p.projw, p.projb, k.f1, R, C, C, s));
+  DVT_TRY(resid_ln(C, k.xin, k.f1, p.ls1, k.x1, p.n2w, p.n2b, k.xn2, k.mean2, k.rstd2, T, Tp, R, d.eps, s));
+  DVT_TRY(blk_lin_fwd(mp, WFC1, k.xn2, p.fc1w, p.fc1b, k.h, R, F, C, s));
+  DVT_TRY(gelu_fwd(k.h, k.a, (int64_t)R * F / 4, s));
+  return blk_lin_fwd(mp, WFC2, k.a, p.fc2w, p.fc2b, k.f2, R, C, F, s);
+}
+
+int block_bwd(const BlockDims& d, const BlockTensors<const float>& p, const BlockTensors<float>& g, const BlockActs& k,
+              const BlockScratch& w, const BlockBf16* mp, bool rows_kernel, bool fuse_softmax_bwd, hipStream_t s) {
+  const int C = d.ad.C, F = d.F, R = d.ad.batch * d.ad.Tp;
+  // mlp: out = x1 + [ls2 (.)] f2
+  const float* dy = w.d0;
+  if (p.ls2) {
+    DVT_TRY(ls_bwd(C, w.d0, k.f2, p.ls2, w.d1, g.ls2, R, s));  // d1 = d f2
+    dy = w.d1;
+  }
+  DVT_TRY(blk_lin_bwd(mp, WFC2, dy, k.a, p.fc2w, w.dh, g.fc2w, g.fc2b, R, C, F, s, w.wT));
+  DVT_TRY(gelu_bwd(k.h, w.dh, (int64_t)R * F / 4, s));
+  DVT_TRY(blk_lin_bwd(mp, WFC1, w.dh, k.xn2, p.fc1w, w.d2, g.fc1w, g.fc1b, R, F, C, s, w.wT));
+  DVT_TRY(ln_bwd(C, w.d2, k.x1, k.mean2, k.rstd2, p.n2w, w.d0, w.d1, g.n2w, g.n2b, R, s));  // d1 = d x1
+  // attention: x1 = xin + [ls1 (.)] f1
+  dy = w.d1;
+  if (p.ls1) {
+    DVT_TRY(ls_bwd(C, w.d1, k.f1, p.ls1, w.d0, g.ls1, R, s));  // d0 = d f1
+    dy = w.d0;
+  }
+  DVT_TRY(blk_lin_bwd(mp, WPROJ, dy, k.ao, p.projw, w.d2, g.projw, g.projb, R, C, C, s, w.wT));  // d2 = d ao
+  DVT_TRY(block_attn_bwd(d.ad, k.qkv, k.P, k.ao, w.d2, w.dqkv, w.dP, w.rowdot, kAttnScale, rows_kernel, fuse_softmax_bwd, s));
+  DVT_TRY(blk_lin_bwd(mp, WQKV, w.dqkv, k.xn1, p.qkvw, w.d2, g.qkvw, g.qkvb, R, 3 * C, C, s, w.wT));
+  return ln_bwd(C, w.d2, k.xin, k.mean1, k.rstd1, p.n1w, w.d1, w.d0, g.n1w, g.n1b, R, s);  // d0 = d xin
+}
+
+void carve_block_acts(Carver& cv, BlockActs* k, int64_t R, int64_t C, int64_t F, int64_t PP, bool own_f) {
+  k->xin = cv.take(R * C);
+  k->xn1 = cv.take(R * C);
+  k->mean1 = cv.take(R);
+  k->rstd1 = cv.take(R);
+  k->qkv = cv.take(R * 3 * C);
+  k->P = cv.take(PP);
+  k->ao = cv.take(R * C);
+  k->f1 = own_f ? cv.take(R * C) : nullptr;
+  k->x1 = cv.take(R * C);
+  k->xn2 = cv.take(R * C);
+  k->mean2 = cv.take(R);
+  k->rstd2 = cv.take(R);
+  k->h = cv.take(R * F);
+  k->a = cv.take(R * F);
+  k->f2 = own_f ? cv.take(R * C) : nullptr;
+}
+
+void carve_block_scratch(Carver& cv, BlockScratch* w, int64_t R, int64_t C, int64_t F, int64_t PP, int64_t rowdot_floats) {
+  w->d0 = cv.take(R * C);
+  w->d1 = cv.take(R * C);
+  w->d2 = cv.take(R * C);
+  w->dh = cv.take(R * F);
+  w->dqkv = cv.take(R * 3 * C);
+  w->dP = cv.take(PP);
+  w->acc = cv.take(64);
+  w->wT = cv.take((3 * C > F ? 3 * C : F) * C);  // one transposed weight matrix, rebuilt in front of each data-gradient GEMM
+  w->rowdot = cv.take(rowdot_floats);            // [batch * heads * Tp] rowsum(dP (.) P) of the softmax backward
 }
 
 // ---- component entry points for tests (include/dvt_parts.h): forwarders to the launchers above; no kernel and no launch of
@@ -655,4 +934,26 @@ extern "C" int dvt_parts_loss_rows(int C, const float* a, const float* b, const 
   if (n_prefix < 0 || T <= n_prefix || Tp < T || R < 1 || (R % Tp) || norm_batch < R / Tp) return DVT_E_BADARG;
   return loss_rows(add != 0, C, a, add ? b : nullptr, target, out, dout, acc, n_prefix, T, Tp, R, norm_batch, loss_out,
                    (hipStream_t)stream);
+}
+
+extern "C" int dvt_parts_add_ln(int C, const float* a, int a_packed, const float* b, int b_is_pos, float* sum_out,
+                                const float* gamma, const float* beta, float* xn, float* mean, float* rstd, int T, int Tp, int R,
+                                float eps, void* stream) {
+  if (!parts_c_ok(C) || !a || !gamma || !beta || !xn || !mean || !rstd || T < 1 || Tp < T || R < 1 || (R % Tp) || !(eps > 0.f))
+    return DVT_E_BADARG;
+  return add_ln(C, a, a_packed, b, b_is_pos, sum_out, gamma, beta, xn, mean, rstd, T, Tp, R, eps, (hipStream_t)stream);
+}
+
+extern "C" int dvt_parts_ls_add_ln(int C, const float* a, const float* f, const float* ls, float* sum_out, const float* gamma,
+                                   const float* beta, float* xn, float* mean, float* rstd, int T, int Tp, int R, float eps,
+                                   void* stream) {
+  if (!parts_c_ok(C) || !a || (ls && !f) || !gamma || !beta || !xn || !mean || !rstd || T < 1 || Tp < T || R < 1 || (R % Tp) ||
+      !(eps > 0.f))
+    return DVT_E_BADARG;
+  return ls_add_ln(C, a, f, ls, sum_out, gamma, beta, xn, mean, rstd, T, Tp, R, eps, (hipStream_t)stream);
+}
+
+extern "C" int dvt_parts_ls_bwd(int C, const float* dy, const float* f, const float* ls, float* df, float* dls, int R, void* stream) {
+  if (!parts_c_ok(C) || !dy || !f || !ls || !df || !dls || R < 1) return DVT_E_BADARG;
+  return ls_bwd(C, dy, f, ls, df, dls, R, (hipStream_t)stream);
 }

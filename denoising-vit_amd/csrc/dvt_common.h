@@ -11,6 +11,13 @@
     if (e__ != hipSuccess) return (int)e__;        \
   } while (0)
 
+// return a callee's non-zero code (DVT_E_* or a hipError_t) from the calling function
+#define DVT_TRY(x)              \
+  do {                          \
+    const int rc__ = (x);       \
+    if (rc__ != 0) return rc__; \
+  } while (0)
+
 static inline int dvt_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 static inline bool dvt_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -298,6 +305,11 @@ int dvt_linear_fwd_big_epi(const float* x, const float* w, const float* b, float
 bool dvt_linear_wgrad_big_ok(int rows, int n, int k);
 int dvt_linear_wgrad_big(const float* dy, const float* x, float* dw, float* db, int rows, int n, int k, int accumulate,
                          hipStream_t s);
+// The fp32 patch-embedding front end (dvt_vit_f32.hip), one block per token row, of the fp32 extractors and of stage 3:
+// col[rows][k_patch] = im2col(img), prefix and padded rows zero;  x = prefix tokens | y + pos | 0 (timm _pos_embed)
+struct DvtVitConfig;
+int dvt_im2col_f32(const float* img, float* col, const DvtVitConfig& c, int rows, hipStream_t s);
+int dvt_embed_f32(const float* y, float* x, const float* prefix, const float* pos, const DvtVitConfig& c, int rows, hipStream_t s);
 // bf16_operands: round operands to bf16 while staging (autocast semantics), fp32 otherwise
 int dvt_linear_group(const DvtLinearOp* ops, int n_ops, hipStream_t s, int bf16_operands = 0);
 int dvt_fit_prep(const DvtGridTable* tbl, const float* xy, const int32_t* ridx, const float* params,

@@ -241,12 +241,6 @@ extern "C" int dvt_field_infer(const DvtFitConfig* c, const float* params, const
 
 namespace {
 
-#define DVT_TRY(x)         \
-  do {                     \
-    int rc__ = (x);        \
-    if (rc__) return rc__; \
-  } while (0)
-
 int check_bufs(const DvtFitConfig* c, const DvtFitBuffers* b, int step_begin, int step_end) {
   int rc = check_cfg(c);
   if (rc) return rc;
@@ -507,7 +501,6 @@ int fit_step(const DvtFitConfig* c, int k, const DvtFitBuffers* const* bs, const
   }
   return 0;
 }
-#undef DVT_TRY
 
 }  // namespace
 

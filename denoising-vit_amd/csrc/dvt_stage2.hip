@@ -6,10 +6,10 @@
 //
 // Everything is exact fp32, like the reference.  The contractions -- linear layers forward / data gradient /
 // weight gradient, and the four attention products per direction -- all go through ONE GEMM kernel family
-// (dvt_gemm_f32_ex, v_mfma_f32_32x32x2_f32 behind a 3-stage LDS-DMA pipeline); the row-local pieces are
-// LayerNorm forward fused with the residual adds, softmax forward/backward and AdamW here, and LayerNorm backward, GELU, the
-// loss with its gradient and the attention launch sequences in dvt_block_train.hip, which the stage-3 step runs as well; this
-// file holds the step's launch sequence.  Attention keeps its probabilities P [batch*heads, Tp, Tp]
+// (dvt_gemm_f32_ex, v_mfma_f32_32x32x2_f32 behind a 3-stage LDS-DMA pipeline).  The block -- its forward and backward launch
+// sequences and every kernel they run but the two unfused softmax passes -- is dvt_block_train.hip's, which the stage-3 step
+// runs as well; this file holds the step around the blocks (input add + norm, unpack or loss, pos_embed gradient), the
+// softmax passes, AdamW and the process's A/B switches.  Attention keeps its probabilities P [batch*heads, Tp, Tp]
 // in HBM: at 288 GB per GPU the 3 GB that costs at batch 32 is cheaper than recomputing QK^T in the backward
 // pass, and P is exactly what dV = P^T dO and dS = P (dP - rowsum(P dP)) need.
 //
@@ -32,61 +32,6 @@ int g_s2_big_bwd = 1;  // DVT_S2_BIG_BWD=0: the data-gradient GEMMs on the 64 x 
 int g_s2_big_fwd = 1;  // DVT_S2_BIG=0 in the environment of the process: the 64 x 64 tile for the forward layers too (A/B)
 
 namespace {
-
-// ==========================================================================================================
-// (a [+ b]) -> sum, LayerNorm(sum) -> xn, per-row mean / rstd.  One wave per row.
-//   a: packed [batch, T, C] (a_packed) or padded [R, C];  b: nullptr, pos_embed [T, C] (b_is_pos) or padded [R, C]
-// Rows t >= T: sum = xn = 0, mean = rstd = 0.
-// online_denoiser.py:88-89 (x + pos_embed), Block: x + attn(norm1(x)), x + mlp(norm2(x)).
-// ==========================================================================================================
-template <int C>
-__global__ __launch_bounds__(256) void s2_add_ln_kernel(const float* __restrict__ a, int a_packed,
-                                                        const float* __restrict__ b, int b_is_pos,
-                                                        float* __restrict__ sum_out, const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, float* __restrict__ xn,
-                                                        float* __restrict__ mean, float* __restrict__ rstd, int T,
-                                                        int Tp, int R, float eps) {
-  const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= R) return;
-  const int img = r / Tp, t = r - img * Tp;
-  Row<C> x;
-  if (t >= T) {
-    x.zero();
-    if (sum_out) x.store(sum_out + (size_t)r * C, lane);
-    x.store(xn + (size_t)r * C, lane);
-    if (lane == 0) {
-      mean[r] = 0.f;
-      rstd[r] = 0.f;
-    }
-    return;
-  }
-  x.load(a_packed ? a + ((size_t)img * T + t) * C : a + (size_t)r * C, lane);
-  if (b) {
-    Row<C> y;
-    y.load(b_is_pos ? b + (size_t)t * C : b + (size_t)r * C, lane);
-    ROW_FOR(j, Row<C>::NJ) x.v[j] = f4_add(x.v[j], y.v[j]);
-  }
-  if (sum_out) x.store(sum_out + (size_t)r * C, lane);
-  const float mu = x.sum() * (1.0f / C);
-  Row<C> d;
-  float ss = 0.f;
-  ROW_FOR(j, Row<C>::NJ) {
-    const int i = lane + 64 * j;
-    d.v[j] = (i < C / 4) ? f4_sub(x.v[j], make_float4(mu, mu, mu, mu)) : make_float4(0.f, 0.f, 0.f, 0.f);
-    ss += f4_dot(d.v[j], d.v[j]);
-  }
-  const float var = wave_sum(ss) * (1.0f / C);
-  const float rs = 1.0f / sqrtf(var + eps);
-  Row<C> g, be;
-  g.load(gamma, lane);
-  be.load(beta, lane);
-  ROW_FOR(j, Row<C>::NJ) d.v[j] = f4_add(f4_mul(f4_scale(d.v[j], rs), g.v[j]), be.v[j]);
-  d.store(xn + (size_t)r * C, lane);
-  if (lane == 0) {
-    mean[r] = mu;
-    rstd[r] = rs;
-  }
-}
 
 // pred[batch, T, C] = a + b (padded rows in, packed rows out): the last residual add of an inference forward
 template <int C>
@@ -215,7 +160,6 @@ struct S2Offsets {
   int64_t t[DVT_S2_MAX_BLOCKS][DVT_S2_TENSORS_PER_BLOCK];
   int64_t total;
 };
-enum { N1W = 0, N1B, QKVW, QKVB, PROJW, PROJB, N2W, N2B, FC1W, FC1B, FC2W, FC2B };
 
 int check_cfg(const DvtS2Config* c) {
   if (!c) return DVT_E_BADARG;
@@ -240,109 +184,60 @@ void offsets(const DvtS2Config* c, S2Offsets* o) {
   o->total = at;
 }
 
-struct S2Block {  // activations a block keeps for its backward pass
-  float *xin, *xn1, *mean1, *rstd1, *qkv, *P, *ao, *x1, *xn2, *mean2, *rstd2, *h, *a;
-};
 struct S2Work {
-  S2Block blk[DVT_S2_MAX_BLOCKS];
-  float *tmp, *d0, *d1, *d2, *dh, *dqkv, *dP, *acc;
-  float* rowdot;  // training: [batch * heads * Tp] rowsum(dP (.) P) of the softmax backward (s2_rowdot_kernel)
-  float* wT;  // training: one transposed weight matrix (max(3 C, F) x C floats), rebuilt in front of each data-gradient GEMM
+  BlockActs blk[DVT_S2_MAX_BLOCKS];
+  BlockScratch g;  // training; inference with several blocks: d0 alone, the ping-pong partner of blk[0].xin
+  float* tmp;      // f1 and f2 of every block: without LayerScale no gradient reads them
 };
 
 int64_t carve(const DvtS2Config* c, int batch, int training, char* base, S2Work* w) {
   const int64_t R = (int64_t)batch * c->tokens_pad, C = c->dim, F = c->mlp_dim;
   const int64_t PP = (int64_t)batch * c->heads * c->tokens_pad * c->tokens_pad;
-  int64_t o = 0;
-  auto take = [&](int64_t floats) {
-    float* p = base ? reinterpret_cast<float*>(base + o) : nullptr;
-    o += (floats * 4 + 255) / 256 * 256;
-    return p;
-  };
+  Carver cv{base};
   S2Work t{};
   const int nb = training ? c->n_blocks : 1;
-  for (int b = 0; b < nb; ++b) {
-    S2Block& k = t.blk[b];
-    k.xin = take(R * C);
-    k.xn1 = take(R * C);
-    k.mean1 = take(R);
-    k.rstd1 = take(R);
-    k.qkv = take(R * 3 * C);
-    k.P = take(PP);
-    k.ao = take(R * C);
-    k.x1 = take(R * C);
-    k.xn2 = take(R * C);
-    k.mean2 = take(R);
-    k.rstd2 = take(R);
-    k.h = take(R * F);
-    k.a = take(R * F);
-  }
+  for (int b = 0; b < nb; ++b) carve_block_acts(cv, &t.blk[b], R, C, F, PP, false);
   for (int b = nb; b < c->n_blocks; ++b) t.blk[b] = t.blk[0];  // inference: every block reuses one set
-  if (!training && c->n_blocks > 1) t.d0 = take(R * C);        // ping-pong partner of blk[0].xin
-  t.tmp = take(R * C);
-  if (training) {
-    t.d0 = take(R * C);
-    t.d1 = take(R * C);
-    t.d2 = take(R * C);
-    t.dh = take(R * F);
-    t.dqkv = take(R * 3 * C);
-    t.dP = take(PP);
-    t.acc = take(64);
-    t.wT = take((3 * C > F ? 3 * C : F) * C);
-    t.rowdot = take((int64_t)batch * c->heads * c->tokens_pad);
-  }
+  if (!training && c->n_blocks > 1) t.g.d0 = cv.take(R * C);   // ping-pong partner of blk[0].xin
+  t.tmp = cv.take(R * C);
+  if (training) carve_block_scratch(cv, &t.g, R, C, F, PP, (int64_t)batch * c->heads * c->tokens_pad);
+  for (int b = 0; b < c->n_blocks; ++b) t.blk[b].f1 = t.blk[b].f2 = t.tmp;
   if (w) *w = t;
-  return o;
-}
-
-int add_ln(int C, const float* a, int a_packed, const float* b, int b_is_pos, float* sum_out, const float* g,
-           const float* be, float* xn, float* mean, float* rstd, int T, int Tp, int R, float eps, hipStream_t s) {
-  switch (C) {
-    case 384: return launch_rows(s2_add_ln_kernel<384>, R, s, a, a_packed, b, b_is_pos, sum_out, g, be, xn, mean, rstd, T, Tp, R, eps);
-    case 768: return launch_rows(s2_add_ln_kernel<768>, R, s, a, a_packed, b, b_is_pos, sum_out, g, be, xn, mean, rstd, T, Tp, R, eps);
-    default: return launch_rows(s2_add_ln_kernel<1024>, R, s, a, a_packed, b, b_is_pos, sum_out, g, be, xn, mean, rstd, T, Tp, R, eps);
-  }
+  return cv.o;
 }
 
 int run(const DvtS2Config* c, const float* params, float* grads, const float* x, const float* target, float* pred,
         int batch, void* work, int64_t work_bytes, float* loss_out, hipStream_t s) {
-  S2_TRY(check_cfg(c));
+  DVT_TRY(check_cfg(c));
   const int training = grads != nullptr;
   if (!params || !x || batch < 1 || !work || (training && (!target || !loss_out)) || (!training && !pred)) return DVT_E_BADARG;
   S2Work w;
   if (carve(c, batch, training, reinterpret_cast<char*>(work), &w) > work_bytes) return DVT_E_BADARG;
   S2Offsets po;
   offsets(c, &po);
-  const int C = c->dim, F = c->mlp_dim, T = c->tokens, Tp = c->tokens_pad, H = c->heads, NB = c->n_blocks;
+  const int C = c->dim, T = c->tokens, Tp = c->tokens_pad, NB = c->n_blocks;
   const int R = batch * Tp;
-  const float scale = 0.125f;  // head_dim^-0.5
   const bool attn_rows = g_s2_attn_rows && Tp % AR_Q == 0;  // s2_attn_rows_kernel walks whole blocks of 128 query rows
-  const AttnDims ad{batch, H, T, Tp, C};
-  auto P = [&](int b, int i) { return params + po.t[b][i]; };
-  auto G = [&](int b, int i) { return grads + po.t[b][i]; };
+  const BlockDims bd{{batch, c->heads, T, Tp, C}, c->mlp_dim, c->ln_eps};
+  auto P = [&](int b) { return block_tensors(params, po.t[b], false); };
+  auto xin = [&](int b) {  // inference with several blocks: block inputs ping-pong
+    return training ? w.blk[b].xin : (b & 1) ? w.g.d0 : w.blk[0].xin;
+  };
 
   // ---- forward ----
-  S2_TRY(add_ln(C, x, 1, c->enable_pe ? params + po.pos : nullptr, 1, w.blk[0].xin, P(0, N1W), P(0, N1B), w.blk[0].xn1,
-                w.blk[0].mean1, w.blk[0].rstd1, T, Tp, R, c->ln_eps, s));
+  DVT_TRY(add_ln(C, x, 1, c->enable_pe ? params + po.pos : nullptr, 1, w.blk[0].xin, P(0).n1w, P(0).n1b, w.blk[0].xn1,
+                 w.blk[0].mean1, w.blk[0].rstd1, T, Tp, R, c->ln_eps, s));
   for (int b = 0; b < NB; ++b) {
-    S2Block k = w.blk[b];
-    if (!training && (b & 1)) k.xin = w.d0;  // inference with several blocks: block inputs ping-pong
-    S2_TRY(lin_fwd(k.xn1, P(b, QKVW), P(b, QKVB), k.qkv, R, 3 * C, C, s));
-    S2_TRY(block_attn_fwd(ad, k.qkv, k.P, k.ao, scale, attn_rows, s));  // P = softmax(scale q k^T), ao = P v
-    S2_TRY(lin_fwd(k.ao, P(b, PROJW), P(b, PROJB), w.tmp, R, C, C, s));
-    S2_TRY(add_ln(C, k.xin, 0, w.tmp, 0, k.x1, P(b, N2W), P(b, N2B), k.xn2, k.mean2, k.rstd2, T, Tp, R, c->ln_eps, s));
-    S2_TRY(lin_fwd(k.xn2, P(b, FC1W), P(b, FC1B), k.h, R, F, C, s));
-    S2_TRY(gelu_fwd(k.h, k.a, (int64_t)R * F / 4, s));
-    S2_TRY(lin_fwd(k.a, P(b, FC2W), P(b, FC2B), w.tmp, R, C, F, s));
+    BlockActs k = w.blk[b];
+    k.xin = xin(b);
+    DVT_TRY(block_fwd(bd, P(b), k, nullptr, attn_rows, s));
     if (b + 1 < NB) {
-      S2Block n = w.blk[b + 1];
-      if (!training && ((b + 1) & 1)) n.xin = w.d0;
-      if (!training && !((b + 1) & 1)) n.xin = w.blk[0].xin;
-      S2_TRY(add_ln(C, k.x1, 0, w.tmp, 0, n.xin, P(b + 1, N1W), P(b + 1, N1B), n.xn1, n.mean1, n.rstd1, T, Tp, R,
-                    c->ln_eps, s));
+      const BlockActs& n = w.blk[b + 1];
+      DVT_TRY(resid_ln(C, k.x1, k.f2, nullptr, xin(b + 1), P(b + 1).n1w, P(b + 1).n1b, n.xn1, n.mean1, n.rstd1, T, Tp, R,
+                       c->ln_eps, s));
     }
   }
-  const S2Block& last = w.blk[NB - 1];
+  const BlockActs& last = w.blk[NB - 1];
   if (!training) {
     switch (C) {
       case 384: return launch_rows(s2_add_unpack_kernel<384>, R, s, (const float*)last.x1, (const float*)w.tmp, pred, T, Tp, R);
@@ -352,25 +247,15 @@ int run(const DvtS2Config* c, const float* params, float* grads, const float* x,
   }
 
   // ---- loss ----
-  S2_TRY(loss_rows(true, C, last.x1, w.tmp, target, pred, w.d0, w.acc, 0, T, Tp, R, batch, loss_out, s));
+  DVT_TRY(loss_rows(true, C, last.x1, w.tmp, target, pred, w.g.d0, w.g.acc, 0, T, Tp, R, batch, loss_out, s));
 
   // ---- backward: d0 holds the gradient w.r.t. the current block's OUTPUT ----
-  for (int b = NB - 1; b >= 0; --b) {
-    const S2Block& k = w.blk[b];
-    // mlp: out = x1 + fc2(gelu(fc1(norm2(x1))))
-    S2_TRY(lin_bwd(w.d0, k.a, P(b, FC2W), w.dh, G(b, FC2W), G(b, FC2B), R, C, F, s, w.wT));
-    S2_TRY(gelu_bwd(k.h, w.dh, (int64_t)R * F / 4, s));
-    S2_TRY(lin_bwd(w.dh, k.xn2, P(b, FC1W), w.d2, G(b, FC1W), G(b, FC1B), R, F, C, s, w.wT));
-    S2_TRY(ln_bwd(C, w.d2, k.x1, k.mean2, k.rstd2, P(b, N2W), w.d0, w.d1, G(b, N2W), G(b, N2B), R, s));  // d1 = d x1
-    // attention: x1 = xin + proj(attn(norm1(xin)))
-    S2_TRY(lin_bwd(w.d1, k.ao, P(b, PROJW), w.d2, G(b, PROJW), G(b, PROJB), R, C, C, s, w.wT));  // d2 = d ao
-    S2_TRY(block_attn_bwd(ad, k.qkv, k.P, k.ao, w.d2, w.dqkv, w.dP, w.rowdot, scale, attn_rows, g_s2_fuse_softmax_bwd != 0, s));
-    S2_TRY(lin_bwd(w.dqkv, k.xn1, P(b, QKVW), w.d2, G(b, QKVW), G(b, QKVB), R, 3 * C, C, s, w.wT));
-    S2_TRY(ln_bwd(C, w.d2, k.xin, k.mean1, k.rstd1, P(b, N1W), w.d1, w.d0, G(b, N1W), G(b, N1B), R, s));  // d0 = d xin
-  }
+  for (int b = NB - 1; b >= 0; --b)
+    DVT_TRY(block_bwd(bd, P(b), block_tensors(grads, po.t[b], false), w.blk[b], w.g, nullptr, attn_rows,
+                      g_s2_fuse_softmax_bwd != 0, s));
   if (c->enable_pe) {
     const int64_t n = (int64_t)T * (C / 4);
-    hipLaunchKernelGGL(s2_pos_grad_kernel, dim3(dvt_cdiv(n, 256)), dim3(256), 0, s, (const float4*)w.d0,
+    hipLaunchKernelGGL(s2_pos_grad_kernel, dim3(dvt_cdiv(n, 256)), dim3(256), 0, s, (const float4*)w.g.d0,
                        (float4*)(grads + po.pos), batch, T, Tp, C / 4);
     DVT_CHECK_LAUNCH();
   }
@@ -381,7 +266,7 @@ int run(const DvtS2Config* c, const float* params, float* grads, const float* x,
 
 extern "C" int dvt_s2_param_offsets(const DvtS2Config* cfg, int64_t* out) {
   if (!out) return DVT_E_BADARG;
-  S2_TRY(check_cfg(cfg));
+  DVT_TRY(check_cfg(cfg));
   S2Offsets o;
   offsets(cfg, &o);
   out[0] = o.pos;
@@ -471,14 +356,6 @@ int s2_softmax_bwd(const float* P, float* dP, int Tp, int64_t rows, float scale,
 
 // ---- component entry points for tests (include/dvt_parts.h): forwarders to the kernels above; no kernel and no launch of
 // their own, every check in front of the first launch ----
-extern "C" int dvt_parts_add_ln(int C, const float* a, int a_packed, const float* b, int b_is_pos, float* sum_out,
-                                const float* gamma, const float* beta, float* xn, float* mean, float* rstd, int T, int Tp, int R,
-                                float eps, void* stream) {
-  if (!parts_c_ok(C) || !a || !gamma || !beta || !xn || !mean || !rstd || T < 1 || Tp < T || R < 1 || (R % Tp) || !(eps > 0.f))
-    return DVT_E_BADARG;
-  return add_ln(C, a, a_packed, b, b_is_pos, sum_out, gamma, beta, xn, mean, rstd, T, Tp, R, eps, (hipStream_t)stream);
-}
-
 extern "C" int dvt_parts_softmax(const float* P, float* S, int T, int Tp, int64_t rows, float scale, int backward, void* stream) {
   if (!S || Tp < 4 || (Tp & 3) || T < 1 || T > Tp || rows < 1 || !dvt_aligned16(S) || (backward != 0 && backward != 1)) return DVT_E_BADARG;
   if (backward && (!P || !dvt_aligned16(P))) return DVT_E_BADARG;

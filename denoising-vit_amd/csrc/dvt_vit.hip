@@ -517,12 +517,6 @@ int vit_launch_rows_out(const float* x, float* out, int batch, int s_pad, int n_
 
 extern "C" int64_t dvt_vit_taps_struct_size(void) { return (int64_t)sizeof(DvtVitTaps); }
 
-#define DVT_TRY(x)         \
-  do {                     \
-    int rc__ = (x);        \
-    if (rc__) return rc__; \
-  } while (0)
-
 // LayerNorm folded into the GEMMs (ln_fold): needs the folded weights, the 8-phase kernel on every GEMM of the
 // block (whole 256-row / 256-column tiles) and is switched by dvt_vit_tune; otherwise the LayerNorm kernels run.
 bool vit_blocks_fold(const VitBlockGeom& g, const DvtVitBlockWeights* blocks, int n) {
@@ -675,7 +669,6 @@ static int vit_forward_run(const DvtVitConfig* c, const DvtVitWeights* w, const 
   DVT_CHECK_LAUNCH();
   return 0;
 }
-#undef DVT_TRY
 
 extern "C" int dvt_vit_forward(const DvtVitConfig* c, const DvtVitWeights* w, const float* img,
                                float* feat, int batch, int n_blocks, void* workspace,

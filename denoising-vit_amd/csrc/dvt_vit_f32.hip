@@ -387,6 +387,21 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(const float* __restr
 
 }  // namespace
 
+// The fp32 front end's two launches (dvt_common.h): the extractors below and the stage-3 step run them.  No checks: the
+// callers' are in front.
+int dvt_im2col_f32(const float* img, float* col, const DvtVitConfig& c, int rows, hipStream_t s) {
+  hipLaunchKernelGGL(im2col_f32_kernel, dim3(rows), dim3(256), 0, s, img, col, c);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
+int dvt_embed_f32(const float* y, float* x, const float* prefix, const float* pos, const DvtVitConfig& c, int rows, hipStream_t s) {
+  hipLaunchKernelGGL(embed_f32_kernel, dim3(rows), dim3(256), 0, s, (const float4*)y, (float4*)x, (const float4*)prefix,
+                     (const float4*)pos, c);
+  DVT_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int64_t dvt_vit_workspace_bytes_f32(const DvtVitConfig* c, int batch) {
   if (!c || batch <= 0 || c->s_pad % 32 || c->dim % 64 || c->dim > 1536 || c->heads * 64 != c->dim) return -1;
   if (c->mlp_kind != DVT_VIT_MLP_GELU && c->mlp_kind != DVT_VIT_MLP_SWIGLU) return -1;
@@ -487,18 +502,10 @@ static int vit_forward_f32x3_run(const DvtVitConfig* c, const DvtVitWeights* w, 
   VitWorkX3 k;
   carve_x3(c, batch, (char*)workspace, &k);
   const int T = batch * c->s_pad, D = c->dim, Tg = (int)rows256(c, batch);
-#define DVT_TRY(x)         \
-  do {                     \
-    int rc__ = (x);        \
-    if (rc__) return rc__; \
-  } while (0)
-  hipLaunchKernelGGL(im2col_f32_kernel, dim3(T), dim3(256), 0, s, img, k.col, *c);
-  DVT_CHECK_LAUNCH();
+  DVT_TRY(dvt_im2col_f32(img, k.col, *c, T, s));
   DVT_TRY(dvt_vit_split3(k.col, k.a3, T, c->k_patch, 0, 0, stream));
   DVT_TRY(dvt_vit_gemm_f32out(k.a3, w->patch_w, w->patch_b, k.ao, Tg, D, 3 * c->k_patch, stream));
-  hipLaunchKernelGGL(embed_f32_kernel, dim3(T), dim3(256), 0, s, (const float4*)k.ao, (float4*)k.x,
-                     (const float4*)w->cls_token, (const float4*)w->pos_embed, *c);
-  DVT_CHECK_LAUNCH();
+  DVT_TRY(dvt_embed_f32(k.ao, k.x, w->cls_token, w->pos_embed, *c, T, s));
   // The GEMMs run over Tg = whole 256-row tiles, embed / LayerNorm write T rows: the phantom rows of the residual stream
   // and of the split A rows start every forward as zeros (they are only ever read row-locally, but the carve depends on
   // `batch`, so without this they could alias another layout's bytes, NaN patterns included -- ADVICE r3)
@@ -542,7 +549,6 @@ static int vit_forward_f32x3_run(const DvtVitConfig* c, const DvtVitWeights* w, 
       ++tap;
     }
   }
-#undef DVT_TRY
   if (taps) return 0;
   const int out_rows = batch * (c->n_tokens - c->n_prefix);
   hipLaunchKernelGGL(layernorm_f32_kernel<true>, dim3(dvt_cdiv(out_rows, 4)), dim3(256), 0, s, k.x, w->norm_w,
@@ -579,9 +585,7 @@ extern "C" int dvt_vit_im2col_f32(const DvtVitConfig* c, const float* img, float
   if (c->patch <= 0 || c->stride <= 0 || c->grid_h <= 0 || c->grid_w <= 0 || 3 * c->patch * c->patch > c->k_patch) return DVT_E_BADARG;
   if (c->n_tokens != c->n_prefix + c->grid_h * c->grid_w) return DVT_E_BADARG;
   if ((c->grid_h - 1) * c->stride + c->patch > c->img_h || (c->grid_w - 1) * c->stride + c->patch > c->img_w) return DVT_E_BADARG;
-  hipLaunchKernelGGL(im2col_f32_kernel, dim3(batch * c->s_pad), dim3(256), 0, (hipStream_t)stream, img, col, *c);
-  DVT_CHECK_LAUNCH();
-  return 0;
+  return dvt_im2col_f32(img, col, *c, batch * c->s_pad, (hipStream_t)stream);
 }
 
 static int vit_forward_f32_run(const DvtVitConfig* c, const DvtVitWeights* w, const float* img, float* feat,
@@ -598,17 +602,9 @@ static int vit_forward_f32_run(const DvtVitConfig* c, const DvtVitWeights* w, co
   const int Tg = (int)rows128(c, batch);  // the linear layers' M (whole 128-row tiles; rows [T, Tg) are never read)
   const long long nqD = (long long)T * D / 4;
   const int ew_blocks = 256 * 8;
-#define DVT_TRY(x)         \
-  do {                     \
-    int rc__ = (x);        \
-    if (rc__) return rc__; \
-  } while (0)
-  hipLaunchKernelGGL(im2col_f32_kernel, dim3(T), dim3(256), 0, s, img, k.col, *c);
-  DVT_CHECK_LAUNCH();
+  DVT_TRY(dvt_im2col_f32(img, k.col, *c, T, s));
   DVT_TRY(dvt_linear_fwd_big(k.col, (const float*)w->patch_w, w->patch_b, k.tmp, Tg, D, c->k_patch, s));
-  hipLaunchKernelGGL(embed_f32_kernel, dim3(T), dim3(256), 0, s, (const float4*)k.tmp, (float4*)k.x,
-                     (const float4*)w->cls_token, (const float4*)w->pos_embed, *c);
-  DVT_CHECK_LAUNCH();
+  DVT_TRY(dvt_embed_f32(k.tmp, k.x, w->cls_token, w->pos_embed, *c, T, s));
   int tap = 0;
   for (int l = 0; l < n_blocks; ++l) {
     const DvtVitBlockWeights& bw = w->blocks[l];
@@ -662,7 +658,6 @@ static int vit_forward_f32_run(const DvtVitConfig* c, const DvtVitWeights* w, co
       ++tap;
     }
   }
-#undef DVT_TRY
   if (taps) return 0;
   const int out_rows = batch * (c->n_tokens - c->n_prefix);
   launch_final_ln_f32(k.x, w->norm_w, w->norm_b, feat, out_rows, D, c->ln_eps, c->s_pad, c->n_tokens, c->n_prefix, s);

@@ -269,8 +269,9 @@ def build(force: bool = False, verbose: bool = False, lab: bool = False) -> Path
     source, compiled in parallel, then one link.  Rebuilds only when a source/header is newer than the library.
     The bf16 ViT extractor is three of those sources -- dvt_vit.hip (forward loop, small kernels), dvt_vit_gemm.hip (GEMMs; its
     epilogues in dvt_vit_epilogue.h) and dvt_vit_attn.hip (attention) -- that share dvt_vit_dev.h and compile side by side.
-    The stage-2 and stage-3 trainers (dvt_stage2.hip, dvt_stage3.hip) share one compiled copy of their block code,
-    dvt_block_train.hip (declared in dvt_block_train.h).
+    The stage-2 and stage-3 trainers (dvt_stage2.hip, dvt_stage3.hip) share one compiled copy of their block,
+    dvt_block_train.hip (declared in dvt_block_train.h): its kernels, its forward / backward launch sequences and its workspace
+    carving; stage 3 takes its im2col and token assembly from the fp32 extractor (dvt_vit_f32.hip, declared in dvt_common.h).
     The exact-fp32 GEMM is three sources by tile family that share dvt_gemm_f32_dev.h: dvt_gemm_f32.hip (register-staged, the
     stage-1 fit), dvt_gemm_f32_glds.hip (LDS-DMA ring, dvt_gemm_f32_ex) and dvt_gemm_f32_big.hip (128 x 128 x 32).  dvt_tune.hip
     is dvt_tune_set alone: every unit decodes the keys of its own knobs (dvt_tune.h).

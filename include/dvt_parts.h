@@ -56,7 +56,7 @@ int dvt_parts_gemm_ex(const DvtPartsGemmEx* g, void* stream);
 int dvt_parts_linear_big_epi(const float* x, const float* w, const float* b, float* y, int m, int n, int k, int epi,
                              const float* gamma, void* stream);
 
-/* ---- dvt_block_train.hip (lin_fwd .. loss_rows, shared by stages 2 and 3) and dvt_stage2.hip (add_ln, softmax, pos_grad) -- */
+/* ---- dvt_block_train.hip (lin_fwd .. loss_rows, add_ln, shared by stages 2 and 3) and dvt_stage2.hip (softmax, pos_grad) -- */
 /* lin_fwd / lin_bwd exactly as the trainers call them; both obey dvt_tune_set(18, mask), the side-stream fork of the
  * weight gradient included (joined before the call returns to the caller's stream order).
  *   y[R][n] = x[R][k] . w[n][k]^T + b
@@ -94,7 +94,8 @@ int dvt_parts_loss_rows(int C, const float* a, const float* b, const float* targ
 /* dpos[t][c] += sum_b dx[b * Tp + t][c], t < T;  C % 4 == 0 */
 int dvt_parts_pos_grad(const float* dx, float* dpos, int batch, int T, int Tp, int C, void* stream);
 
-/* ---- dvt_stage3.hip ---------------------------------------------------------------------------------------- */
+/* ---- dvt_block_train.hip (ls_add_ln, ls_bwd) and dvt_stage3.hip (the embedding; s3_embed and s3_im2col launch the fp32
+ * extractor's kernels of dvt_vit_f32.hip, which stage 3 runs) ---- */
 /* sum = a + ls (.) f (ls NULL: sum = a), then as dvt_parts_add_ln (all rows padded [R][C]) */
 int dvt_parts_ls_add_ln(int C, const float* a, const float* f, const float* ls, float* sum_out, const float* gamma,
                         const float* beta, float* xn, float* mean, float* rstd, int T, int Tp, int R, float eps, void* stream);

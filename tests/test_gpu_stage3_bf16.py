@@ -191,6 +191,27 @@ def test_default_path_keeps_the_parents_bits(golden_dir, case, route):
         assert err <= H.tolerance(values, spread), (k, err, H.tolerance(values, spread))
 
 
+def test_bf16_path_keeps_the_parents_bits(golden_dir):
+    """The bf16 mode's routing moved into the block the two trainers share: one gemm_mode 1 step at the first shape against
+    what `tools/record_s3_parent_digests.py --bf16` recorded from the commit before that move
+    (tests/golden/s3_bf16_parent_digests.json), split by the recorder's rule as above: a digest for every tensor that is
+    not summed with atomics and kept its bits over the parent's repeats, the recorded values within twice the parent's own
+    spread (4-ulp floor) for the rest."""
+    rec_mod, H = _recorder("record_s3_parent_digests"), _recorder("record_s3_golden")
+    with open(os.path.join(golden_dir, "s3_bf16_parent_digests.json")) as f:
+        rec = json.load(f)
+    got = rec_mod.step_tensors(torch, "s384x2", "mp1")
+    want, varies = rec["cases"]["s384x2"], rec["varies"]["s384x2"]
+    assert set(got) == set(want) | set(varies) and all(H.is_atomic(k) or k in rec["observed"]["s384x2"] for k in varies)
+    wrong = [k for k in want if H.digest(got[k]) != want[k]]
+    assert not wrong, wrong
+    for k, r in varies.items():
+        values, spread = H.unpack(torch, r)
+        err = float((got[k] - values).abs().max())
+        print(f"  {k}: |got - recorded| {err:.3e}, bound {H.tolerance(values, spread):.3e}")
+        assert err <= H.tolerance(values, spread), (k, err, H.tolerance(values, spread))
+
+
 def test_extractor_keeps_the_parents_bits(golden_dir):
     """The bf16 GEMM unit is shared with the extractor: a 2-block ViT-B/14 bf16 forward still gives the bits of
     tests/golden/vitb_2block_parent.json (the route of tests/test_gpu_vitg.py), also AFTER a bf16 stage-3 step has run its
