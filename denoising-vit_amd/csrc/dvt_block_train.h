@@ -103,6 +103,15 @@ struct BlockScratch {  // one set for all blocks: the backward's gradients in fl
 };
 struct BlockBf16 {  // stage 3's gemm_mode 1: the qkv / proj / fc1 / fc2 weights as bf16, [n, k] and transposed [k, n], and the
   uint16_t *w[4], *wt[4], *abf;  // scratch the A operand of the GEMM about to run is rounded into
+  // gemm_mode 3 (aq non-null): the block's attention is the bf16 flash attention of dvt_s3_attn.hip.  The forward keeps aq =
+  // bf16 (q log2(e) / 8, k, v) [3][batch * heads][Tp][64] and lse [batch * heads][Tp] of THIS block; BlockActs::qkv is then
+  // fp32 scratch that only the forward touches (one buffer for all blocks), P and dP are not used
+  uint16_t* aq;
+  float* lse;
+  // ... and qkv_db [3 C] (one for all blocks) receives the column sums of dqkv, of which the backward adds the q and v thirds
+  // to the bias gradient: the k third of a qkv bias has NO gradient (a softmax row ignores a common shift of its logits), what
+  // the rounded dS leaves there is noise, and AdamW would walk the k bias by a learning rate per step on it
+  float* qkv_db;
 };
 struct BlockDims {
   AttnDims ad;
@@ -113,7 +122,8 @@ struct BlockDims {
 // f2 = fc2(gelu(fc1(xn2))) written and NOT added: f1 and f2 are the caller's (a block's own, or one buffer for both where no
 // LayerScale gradient reads them), and the residual add of f2 with the norm behind it is the caller's resid_ln.  block_bwd
 // takes d0 = d(block output), leaves d0 = d xin and uses d1, d2, dh, dqkv, dP, rowdot, wT as scratch.
-// mp null: exact fp32; else forward and data-gradient GEMMs on bf16 operands, weight gradients exact all the same.
+// mp null: exact fp32; else forward and data-gradient GEMMs on bf16 operands, weight gradients exact all the same, and with
+// mp->aq the flash attention in place of the fp32 products (rows_kernel / fuse_softmax_bwd then choose nothing).
 int block_fwd(const BlockDims& d, const BlockTensors<const float>& p, const BlockActs& k, const BlockBf16* mp, bool rows_kernel,
               hipStream_t s);
 int block_bwd(const BlockDims& d, const BlockTensors<const float>& p, const BlockTensors<float>& g, const BlockActs& k,
@@ -129,6 +139,7 @@ struct Carver {
     return p;
   }
 };
-// R rows, C columns, F mlp columns, PP floats of P.  own_f: f1 behind ao and f2 at the end, else both left null
-void carve_block_acts(Carver& cv, BlockActs* k, int64_t R, int64_t C, int64_t F, int64_t PP, bool own_f);
+// R rows, C columns, F mlp columns, PP floats of P.  own_f: f1 behind ao and f2 at the end, else both left null; own_qkv
+// likewise (stage 3's gemm_mode 3 points every block's qkv at one scratch buffer)
+void carve_block_acts(Carver& cv, BlockActs* k, int64_t R, int64_t C, int64_t F, int64_t PP, bool own_f, bool own_qkv = true);
 void carve_block_scratch(Carver& cv, BlockScratch* w, int64_t R, int64_t C, int64_t F, int64_t PP, int64_t rowdot_floats);

@@ -517,6 +517,12 @@ __global__ __launch_bounds__(256) void s2_transpose_kernel(const float* __restri
   for (int i = 0; i < 4; ++i) out[(size_t)(k0 + ty + 8 * i) * n + n0 + tx] = tile[tx][ty + 8 * i];
 }
 
+// gb[c] += db[c] for the q and v thirds of a qkv bias gradient [3 C]; the k third [C, 2 C) is left alone
+__global__ __launch_bounds__(256) void s3_qv_bias_kernel(const float* __restrict__ db, float* __restrict__ gb, int C) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c < 3 * C && (c < C || c >= 2 * C)) gb[c] += db[c];
+}
+
 template <bool ADD>
 int loss_rows_t(int C, const float* a, const float* b, const float* target, float* out, float* dout, float* acc, int n_prefix,
                 int T, int Tp, int R, float inv_el, float inv_tok, hipStream_t s) {
@@ -820,7 +826,10 @@ int block_fwd(const BlockDims& d, const BlockTensors<const float>& p, const Bloc
               hipStream_t s) {
   const int C = d.ad.C, F = d.F, T = d.ad.T, Tp = d.ad.Tp, R = d.ad.batch * Tp;
   DVT_TRY(blk_lin_fwd(mp, WQKV, k.xn1, p.qkvw, p.qkvb, k.qkv, R, 3 * C, C, s));
-  DVT_TRY(block_attn_fwd(d.ad, k.qkv, k.P, k.ao, kAttnScale, rows_kernel, s));  // P = softmax(scale q k^T), ao = P v
+  if (mp && mp->aq)  // gemm_mode 3: ao and lse, no P
+    DVT_TRY(dvt_s3_attn_fwd(k.qkv, mp->aq, k.ao, mp->lse, d.ad.batch, d.ad.heads, T, Tp, s));
+  else
+    DVT_TRY(block_attn_fwd(d.ad, k.qkv, k.P, k.ao, kAttnScale, rows_kernel, s));  // P = softmax(scale q k^T), ao = P v
   DVT_TRY(blk_lin_fwd(mp, WPROJ, k.ao, p.projw, p.projb, k.f1, R, C, C, s));
   DVT_TRY(resid_ln(C, k.xin, k.f1, p.ls1, k.x1, p.n2w, p.n2b, k.xn2, k.mean2, k.rstd2, T, Tp, R, d.eps, s));
   DVT_TRY(blk_lin_fwd(mp, WFC1, k.xn2, p.fc1w, p.fc1b, k.h, R, F, C, s));
@@ -848,17 +857,28 @@ int block_bwd(const BlockDims& d, const BlockTensors<const float>& p, const Bloc
     dy = w.d0;
   }
   DVT_TRY(blk_lin_bwd(mp, WPROJ, dy, k.ao, p.projw, w.d2, g.projw, g.projb, R, C, C, s, w.wT));  // d2 = d ao
-  DVT_TRY(block_attn_bwd(d.ad, k.qkv, k.P, k.ao, w.d2, w.dqkv, w.dP, w.rowdot, kAttnScale, rows_kernel, fuse_softmax_bwd, s));
-  DVT_TRY(blk_lin_bwd(mp, WQKV, w.dqkv, k.xn1, p.qkvw, w.d2, g.qkvw, g.qkvb, R, 3 * C, C, s, w.wT));
+  if (mp && mp->aq)
+    DVT_TRY(dvt_s3_attn_bwd(mp->aq, k.ao, w.d2, mp->lse, w.rowdot, w.dqkv, d.ad.batch, d.ad.heads, d.ad.T, d.ad.Tp, s));
+  else
+    DVT_TRY(block_attn_bwd(d.ad, k.qkv, k.P, k.ao, w.d2, w.dqkv, w.dP, w.rowdot, kAttnScale, rows_kernel, fuse_softmax_bwd, s));
+  if (mp && mp->aq) {  // the bias gradient without its k third, which is identically zero (BlockBf16)
+    const hipError_t e = hipMemsetAsync(mp->qkv_db, 0, sizeof(float) * 3 * C, s);
+    if (e != hipSuccess) return (int)e;
+    DVT_TRY(blk_lin_bwd(mp, WQKV, w.dqkv, k.xn1, p.qkvw, w.d2, g.qkvw, mp->qkv_db, R, 3 * C, C, s, w.wT));
+    hipLaunchKernelGGL(s3_qv_bias_kernel, dim3(dvt_cdiv(3 * C, 256)), dim3(256), 0, s, (const float*)mp->qkv_db, g.qkvb, C);
+    DVT_CHECK_LAUNCH();
+  } else {
+    DVT_TRY(blk_lin_bwd(mp, WQKV, w.dqkv, k.xn1, p.qkvw, w.d2, g.qkvw, g.qkvb, R, 3 * C, C, s, w.wT));
+  }
   return ln_bwd(C, w.d2, k.xin, k.mean1, k.rstd1, p.n1w, w.d1, w.d0, g.n1w, g.n1b, R, s);  // d0 = d xin
 }
 
-void carve_block_acts(Carver& cv, BlockActs* k, int64_t R, int64_t C, int64_t F, int64_t PP, bool own_f) {
+void carve_block_acts(Carver& cv, BlockActs* k, int64_t R, int64_t C, int64_t F, int64_t PP, bool own_f, bool own_qkv) {
   k->xin = cv.take(R * C);
   k->xn1 = cv.take(R * C);
   k->mean1 = cv.take(R);
   k->rstd1 = cv.take(R);
-  k->qkv = cv.take(R * 3 * C);
+  k->qkv = own_qkv ? cv.take(R * 3 * C) : nullptr;
   k->P = cv.take(PP);
   k->ao = cv.take(R * C);
   k->f1 = own_f ? cv.take(R * C) : nullptr;

@@ -35,6 +35,7 @@ HIP_SOURCES = [
     "dvt_stage2.hip",
     "dvt_stage3.hip",
     "dvt_s3_cast.hip",
+    "dvt_s3_attn.hip",
     "dvt_seg.hip",
     "dvt_depth.hip",
     "dvt_vis.hip",

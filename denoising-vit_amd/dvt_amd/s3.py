@@ -15,6 +15,8 @@ interpolation tables come from torch itself, once per engine (`pos_tables`).
 `dtype="bfloat16"` (default "float32": exact fp32 throughout) is the opt-in mixed-precision step of include/dvt_stage3.h
 (gemm_mode 1): the forward and data-gradient GEMMs of the blocks' four linear layers run on the extractor's bf16 MFMA GEMM with
 operands rounded to bf16; weight gradients, arenas, activations and everything that is not one of those GEMMs stay fp32.
+`attention="bfloat16"` on top of it (gemm_mode 3; refused with dtype="float32") runs the blocks' attention as the bf16 flash
+attention of csrc/dvt_s3_attn.hip: no probabilities are kept, so the workspace per image shrinks and `slice_size` grows.
 """
 from __future__ import annotations
 
@@ -47,9 +49,43 @@ _lib.register_signatures({
                                        _P]),
     "dvt_s3_cast_bf16": (_I, [_P, _P, C.c_int64, _I, _P]),
     "dvt_s3_cast_bf16_t": (_I, [_P, _P, _I, _I, _P]),
+    "dvt_s3_attn_operand_bytes": (C.c_int64, [_I, _I, _I]),
+    "dvt_s3_attn_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "dvt_s3_attn_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
 })
 
-GEMM_MODES = {"float32": 0, "bfloat16": 1}  # Stage3Engine(dtype=) -> gemm_mode of dvt_s3_train_slice_pos_mp
+# gemm_mode of dvt_s3_train_slice_pos_mp is a bit set: Stage3Engine(dtype=) gives bit 0, Stage3Engine(attention=) bit 1
+GEMM_MODES = {"float32": 0, "bfloat16": 1}
+ATTENTION_MODES = {"float32": 0, "bfloat16": 2}
+ATTENTION_NEEDS_BF16 = ('attention="bfloat16" is built on the bf16 GEMM mode: it needs dtype="bfloat16" '
+                        "(--attention bfloat16 needs --dtype bfloat16)")
+
+
+def attn_fwd(qkv: torch.Tensor, batch: int, heads: int, n_valid: int):
+    """dvt_s3_attn_fwd on its own: qkv fp32 [batch * Tp, 3 * 64 * heads] (device) -> (ao fp32 [batch * Tp, 64 * heads],
+    lse fp32 [batch * heads, Tp] in log2 units, the bf16 operands [3, batch * heads, Tp, 64] that `attn_bwd` reads)."""
+    _lib.require_cuda(qkv)
+    R, C = qkv.shape[0], qkv.shape[1] // 3
+    Tp = R // batch
+    qkvb = torch.empty(3, batch * heads, Tp, 64, device=qkv.device, dtype=torch.bfloat16)
+    ao = torch.empty(R, C, device=qkv.device, dtype=torch.float32)
+    lse = torch.empty(batch * heads, Tp, device=qkv.device, dtype=torch.float32)
+    _lib.check(_lib.lib().dvt_s3_attn_fwd(_lib.ptr(qkv), _lib.ptr(qkvb), _lib.ptr(ao), _lib.ptr(lse), batch, heads, n_valid, Tp,
+                                          _lib.stream()), "dvt_s3_attn_fwd")
+    return ao, lse, qkvb
+
+
+def attn_bwd(qkvb: torch.Tensor, ao: torch.Tensor, dao: torch.Tensor, lse: torch.Tensor, batch: int, heads: int,
+             n_valid: int) -> torch.Tensor:
+    """dvt_s3_attn_bwd on its own: -> dqkv fp32 [batch * Tp, 3 * 64 * heads] (dq | dk | dv)."""
+    _lib.require_cuda(qkvb, ao, dao, lse)
+    R, C = ao.shape
+    Tp = R // batch
+    dqkv = torch.empty(R, 3 * C, device=ao.device, dtype=torch.float32)
+    D = torch.empty(batch * heads, Tp, device=ao.device, dtype=torch.float32)
+    _lib.check(_lib.lib().dvt_s3_attn_bwd(_lib.ptr(qkvb), _lib.ptr(ao), _lib.ptr(dao), _lib.ptr(lse), _lib.ptr(D), _lib.ptr(dqkv),
+                                          batch, heads, n_valid, Tp, _lib.stream()), "dvt_s3_attn_bwd")
+    return dqkv
 
 
 def cast_bf16(x: torch.Tensor) -> torch.Tensor:
@@ -153,15 +189,17 @@ def param_layout(cfg: VitConfig, pos_grid: int | None = None):
 
 class Stage3Engine(FlatAdamW):
     def __init__(self, cfg: VitConfig, device: torch.device, pos_grid: int | None = None,
-                 max_work_bytes: int | None = None, dtype: str = "float32"):
+                 max_work_bytes: int | None = None, dtype: str = "float32", attention: str = "float32"):
         """`pos_grid`: the grid g0 of the checkpoint's position table when `pos_embed` is to keep its [1, cls + g0 g0, dim]
         shape and be resampled to the run's grid in every step; None: the table is at the run's grid (the layout and the
         calls without a resample).
         `max_work_bytes`: budget of the activation workspace (default: 80 % of the device memory free after the
         arenas are allocated); `train_step` splits a batch into slices that fit.
         `dtype`: "float32" (exact fp32, the default) or "bfloat16": bf16 operands in the forward and data-gradient GEMMs of
-        the blocks' linear layers (see the module's docstring); the arenas and the checkpoint are fp32 either way."""
-        self.set_dtype(dtype)
+        the blocks' linear layers (see the module's docstring); the arenas and the checkpoint are fp32 either way.
+        `attention`: "float32" (the default: fp32 products, probabilities kept) or, with dtype="bfloat16" only, "bfloat16":
+        the blocks' attention as bf16 flash attention, which keeps a log-sum-exp per row instead of the probabilities."""
+        self.set_dtype(dtype, attention)
         if torch.device(device).type != "cuda":
             raise _lib.DvtError("the stage-3 engine needs a HIP device; there is no CPU fallback")
         self.cfg = cfg
@@ -175,13 +213,18 @@ class Stage3Engine(FlatAdamW):
         self._slice_loss = torch.zeros(4, device=self.device, dtype=torch.float32)
         self.max_work_bytes = max_work_bytes
 
-    def set_dtype(self, dtype: str) -> None:
+    def set_dtype(self, dtype: str, attention: str = "float32") -> None:
         """Arithmetic of the following steps.  The state is fp32 either way, so the dtype may change between steps (the
         interleaved A/B of tools/bench_stage3.py does); the workspace grows on demand."""
         if dtype not in GEMM_MODES:
             raise _lib.DvtError(f"the stage-3 step computes in {sorted(GEMM_MODES)}, got dtype={dtype!r}")
+        if attention not in ATTENTION_MODES:
+            raise _lib.DvtError(f"the stage-3 attention computes in {sorted(ATTENTION_MODES)}, got attention={attention!r}")
+        if attention == "bfloat16" and dtype != "bfloat16":
+            raise _lib.DvtError(ATTENTION_NEEDS_BF16)
         self.dtype = dtype
-        self.gemm_mode = GEMM_MODES[dtype]
+        self.attention = attention
+        self.gemm_mode = GEMM_MODES[dtype] | ATTENTION_MODES[attention]
 
     # ---- parameters -------------------------------------------------------------------------------
     def load_timm(self, state: dict) -> None:

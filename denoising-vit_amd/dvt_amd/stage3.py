@@ -30,7 +30,8 @@ Deviations, all forced or harmless:
   * PCA visualisations are not written (`--vis_freq` / `--num_vis_samples` are accepted).
   * `--dtype bfloat16` (default float32, what the reference trains in) is an opt-in mixed-precision student step: see
     dvt_amd/s3.py and include/dvt_stage3.h.  Parameters, optimizer state and checkpoints are fp32 either way, so a
-    checkpoint written under one dtype starts a run under the other through `--vit_checkpoint`.
+    checkpoint written under one dtype starts a run under the other through `--vit_checkpoint`.  `--attention bfloat16`
+    (default float32) adds the bf16 flash attention on top of `--dtype bfloat16` and is refused without it.
   * the ViT weights come from `--vit_checkpoint` (a timm-layout state dict, or a stage-3 checkpoint) because timm cannot
     download here; `--allow_random_vit` runs on random weights (tests and plumbing only).
 """
@@ -249,7 +250,15 @@ def get_args(argv=None):
                    help="float32 (default): the student's step in exact fp32, as the reference trains.  bfloat16: the forward "
                         "and data-gradient GEMMs of the blocks' linear layers take bf16 operands (fp32 accumulation); weight "
                         "gradients, parameters, optimizer state, checkpoints and the teacher stay fp32")
+    p.add_argument("--attention", default="float32", choices=["float32", "bfloat16"],
+                   help="float32 (default): the student's attention as fp32 products with the probabilities kept.  bfloat16 "
+                        "(needs --dtype bfloat16): bf16 flash attention -- q, k, v, P, dS and d ao are rounded to bf16 as "
+                        "matrix operands, accumulation in fp32; the backward recomputes the probabilities from a per-row "
+                        "log-sum-exp, so no [tokens, tokens] matrix is kept and larger slices fit")
     args = p.parse_args(argv)
+    if args.attention == "bfloat16" and args.dtype != "bfloat16":
+        from .s3 import ATTENTION_NEEDS_BF16
+        raise SystemExit("stage 3: " + ATTENTION_NEEDS_BF16)
     if isinstance(args.input_size, int):
         args.input_size = (args.input_size, args.input_size)
     elif len(args.input_size) == 1:
@@ -331,7 +340,7 @@ def build_models(args, device):
     if pos_grid is not None:
         print(f"stage 3: position table {g0} x {g0} resampled to {gh} x {gw} in every step", flush=True)
     student = Stage3Engine(make_config(dim, depth, patch, args.stride_size, *args.input_size, n_reg), device,
-                           pos_grid=pos_grid, dtype=args.dtype)
+                           pos_grid=pos_grid, dtype=args.dtype, attention=args.attention)
     student.load_timm(vit._state_dict)
     return student, teacher
 
@@ -353,6 +362,9 @@ def train(args, rank: int, world: int, device: torch.device, model_factory=None)
         print(f"stage 3: student step dtype {args.dtype}"
               + (" (bf16 operands in the forward and data-gradient GEMMs of the linear layers; weight gradients, state and "
                  "checkpoints fp32)" if args.dtype == "bfloat16" else " (exact fp32)"), flush=True)
+        print(f"stage 3: student attention {args.attention}"
+              + (" (bf16 flash attention: fp32 accumulation, probabilities recomputed in the backward pass, none kept)"
+                 if args.attention == "bfloat16" else " (fp32 products, probabilities kept)"), flush=True)
     misc.fix_random_seeds(args.seed)
     eng, teacher = (model_factory or build_models)(args, device)
     if distributed:  # DistributedDataParallel broadcasts rank 0's parameters at construction

@@ -26,6 +26,15 @@
  * assembly are fp32 as above.  A product of K terms then carries about 2^-9 sqrt(2) relative error per term instead of
  * 2^-24: gradients agree with float64 to some 1e-2 relative L2 per tensor instead of 1e-5.  The default is exact fp32.
  *
+ * gemm_mode 3 (bit 0: the bf16 GEMMs of mode 1, bit 1: bf16 attention) is mode 1 plus a block's attention as a bf16-operand, fp32-accumulate flash attention (csrc/dvt_s3_attn.hip):
+ * q log2(e) / 8, k and v are rounded once to bf16, P is rounded for P v; the forward keeps ao in fp32 and one fp32 log-sum-exp
+ * per query row, no probabilities; the backward recomputes P = 2^(s - lse) per tile and forms dv = P^T dao, dS = P (.) (dao v^T
+ * - D), dq = dS k / 8, dk = dS^T q / 8 with dao, P and dS rounded to bf16 as operands and D = dao . ao in fp32.  No float
+ * atomics.  The k third of a qkv bias gradient, which is identically zero (a softmax row ignores a common shift of its logits) and
+ * would otherwise receive the rounding residue of dS, is not accumulated: mode 3 adds nothing to it.  Neither P nor a block's fp32 qkv is kept (ViT-B/14 at 518 x 518: 95 MB + 13 MB per image and block less, 6.5 MB of
+ * bf16 operands more).  Everything else -- the teacher, parameters, gradients, AdamW state, checkpoints, LayerNorm,
+ * LayerScale, GELU, the loss, the weight gradients, the patch embedding and the position resample -- is as in mode 1.
+ *
  * Conventions as in dvt_hip.h: int return codes (0 = ok, DVT_E_* / hipError_t otherwise), device pointers owned by the
  * caller, `stream` is a hipStream_t, nothing synchronises.
  */
@@ -110,14 +119,17 @@ int dvt_s3_train_slice_pos(const DvtVitConfig* cfg, int g0, const float* wy, con
 
 /* ---- opt-in mixed precision (see "Arithmetic" at the top) -------------------------------------------------------------
  * gemm_mode: 0 = exact fp32 (the call IS dvt_s3_train_slice_pos -- dvt_s3_train_slice for g0 = 0 -- and the workspace theirs),
- *            1 = bf16 operands in the forward and data-gradient GEMMs of qkv / proj / fc1 / fc2, everything else as in 0.
- * Mode 1 rounds the four weights of every block once per call into the workspace (as stored for the forward, transposed for
+ *            1 = bf16 operands in the forward and data-gradient GEMMs of qkv / proj / fc1 / fc2, everything else as in 0,
+ *            3 = mode 1 and the bf16 flash attention (its workspace: mode 1's less every block's P, the dP scratch and every
+ *                block's fp32 qkv, plus 6 dim + 4 heads bytes per token row and block and 12 dim bytes).  The value is a bit set -- 1: the bf16
+ *                GEMMs, 2: the bf16 attention -- and the attention is built on the GEMM mode: 2 alone is refused.
+ * Modes 1 and 3 round the four weights of every block once per call into the workspace (as stored for the forward, transposed for
  * the data gradient: params change between steps, and each slice rounds the same weights, so slices stay additive) and each
  * A operand into one shared scratch right before its GEMM; the workspace grows by 4 bytes per block weight and
  * 2 max(mlp_dim, 3 dim) bytes per token row, behind mode 0's carving.  g0 as for the _pos calls, or 0: the table is at the
  * run's grid, the layout of dvt_s3_param_offsets and the step of dvt_s3_train_slice (wy, wx ignored).  DVT_E_BADARG (-1 for the
  * size) before any launch: another gemm_mode, g0 < 0, a workspace below the mode's
- * size, a null pointer, in mode 1 `params` or `work` not 16-byte aligned. */
+ * size, a null pointer, in modes 1 and 3 `params` or `work` not 16-byte aligned. */
 int64_t dvt_s3_workspace_bytes_mp(const DvtVitConfig* cfg, int batch, int g0, int gemm_mode);
 int dvt_s3_train_slice_pos_mp(const DvtVitConfig* cfg, int g0, const float* wy, const float* wx, int gemm_mode,
                               const float* params, float* grads, const float* img, const float* target, float* feat_out,
@@ -130,6 +142,21 @@ int dvt_s3_train_slice_pos_mp(const DvtVitConfig* cfg, int g0, const float* wy, 
  * Pointers 16-byte aligned; DVT_E_BADARG otherwise, nothing launched. */
 int dvt_s3_cast_bf16(const float* x, void* y, int64_t rows, int n, void* stream);
 int dvt_s3_cast_bf16_t(const float* w, void* wt, int n, int k, void* stream);
+
+/* gemm_mode 3's attention, exported for tests (csrc/dvt_s3_attn.hip).  Head dimension 64, C = 64 heads, R = batch Tp token rows
+ * of which the first T of every image are valid; keys >= T are masked.  No float atomics: two runs give the same bits.
+ *   dvt_s3_attn_fwd: qkv fp32 [R, 3 C] (q | k | v) -> qkvb, the bf16 operands the backward reads again
+ *       ([3][batch heads][Tp][64]: q log2(e) / 8, k, v, each rounded once; dvt_s3_attn_operand_bytes bytes),
+ *       ao fp32 [R, C] = softmax(q k^T / 8) v and lse fp32 [batch heads, Tp] = log2 sum_k 2^(q' . k), q' the rounded scaled q.
+ *       Rows t >= T: ao = 0, lse = 0.
+ *   dvt_s3_attn_bwd: dao = d ao fp32 [R, C] -> dqkv fp32 [R, 3 C] (dq | dk | dv), every element written, rows t >= T zero;
+ *       D [batch heads, Tp] is scratch (it receives rowsum(dao (.) ao)).  P = 2^(q' . k - lse) is recomputed.
+ * DVT_E_BADARG, nothing launched: a null pointer, batch or heads < 1, Tp % 128 != 0, T < 1, T > Tp, qkv / qkvb / ao / dao /
+ * dqkv not 16-byte aligned, more than 2^31 - 1 elements in qkv. */
+int64_t dvt_s3_attn_operand_bytes(int batch, int heads, int Tp);
+int dvt_s3_attn_fwd(const float* qkv, void* qkvb, float* ao, float* lse, int batch, int heads, int T, int Tp, void* stream);
+int dvt_s3_attn_bwd(const void* qkvb, const float* ao, const float* dao, const float* lse, float* D, float* dqkv, int batch,
+                    int heads, int T, int Tp, void* stream);
 
 #ifdef __cplusplus
 }

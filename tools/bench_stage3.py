@@ -1,5 +1,6 @@
 """Time the stage-3 student step (csrc/dvt_stage3.hip): forward + loss + backward + AdamW of a whole ViT, in exact fp32 or
-in the opt-in bf16 mode (`--dtype bfloat16`: bf16 operands in the forward and data-gradient GEMMs of the linear layers).
+in the opt-in bf16 mode (`--dtype bfloat16`: bf16 operands in the forward and data-gradient GEMMs of the linear layers), with
+`--attention bfloat16` on top of it the bf16 flash attention (no probabilities kept).
 
 Prints one JSON line: ms per step, images/s, and the step's matrix FLOPs per second against the 157 TF/s fp32 MFMA peak
 of the MI355X.  The FLOPs count the student only (forward 1x, backward 2x; tokens padded to s_pad rows as the kernels
@@ -8,13 +9,16 @@ student's step) is not part of the timed step.
 
     python tools/bench_stage3.py [--dim 768 --depth 12 --img 518 --batch 64 --steps 3 --warmup 1]
                                  [--input_size H W] [--stride_size S] [--pos_grid G0]
-                                 [--dtype float32|bfloat16] [--ab N]
+                                 [--dtype float32|bfloat16] [--attention float32|bfloat16] [--ab N]
 
-`--ab N`: an interleaved A/B of the two dtypes in one process on one engine -- fp32 step, bf16 step, fp32 step, ... N of
-each after the warm-up of both, every step timed on its own (device synchronised on both sides).  The clock of the chip
+`--ab N`: an interleaved A/B of the three arithmetics in one process on one engine -- fp32 step, bf16 step, bf16 step with
+bf16 attention, fp32 step, ... N of each after the warm-up of all, every step timed on its own (device synchronised on both
+sides).  The clock of the chip
 drifts over a run, so two runs one after the other do not compare; alternating steps see the same clock.  The JSON line then
-carries per dtype the median, minimum and maximum ms per step, and `bf16_faster_than_fp32_spread`: whether the bf16 median
-lies below the fp32 median by more than the fp32 leg's own min-max spread.
+carries per leg the median, minimum and maximum ms per step and the workspace bytes per image of its mode (the increment of
+the workspace from one image to two), `bf16_faster_than_fp32_spread`: whether the bf16 median lies below the fp32 median by
+more than the fp32 leg's own min-max spread, and `bf16_attn_faster_than_bf16_spread`: the same for the attention leg against
+the bf16 leg.  All legs run the same slicing: the one the largest workspace (bf16, fp32 attention) allows.
 
 `--input_size` / `--stride_size` set another geometry than `--img` square at stride 14; `--pos_grid G0` keeps the position
 table at G0 x G0 (37 for the DINOv2 checkpoints) and resamples it to the run's grid in every step, e.g.
@@ -58,14 +62,16 @@ def main():
     p.add_argument("--input_size", type=int, nargs=2, default=None, metavar=("H", "W"), help="default: --img square")
     p.add_argument("--stride_size", type=int, default=14)
     p.add_argument("--dtype", default="float32", choices=["float32", "bfloat16"])
-    p.add_argument("--ab", type=int, default=0, metavar="N", help="interleaved fp32 / bf16 A/B, N timed steps of each")
+    p.add_argument("--attention", default="float32", choices=["float32", "bfloat16"], help="bfloat16 needs --dtype bfloat16")
+    p.add_argument("--ab", type=int, default=0, metavar="N",
+                   help="interleaved fp32 / bf16 / bf16 + bf16 attention A/B, N timed steps of each")
     p.add_argument("--pos_grid", type=int, default=None,
                    help="grid of the position table when it is not the run's (resampled in every step); default: the run's")
     a = p.parse_args()
     dev = torch.device("cuda:0")
     H, W = a.input_size or (a.img, a.img)
     cfg = s3.make_config(a.dim, a.depth, 14, a.stride_size, H, W)
-    eng = s3.Stage3Engine(cfg, dev, pos_grid=a.pos_grid, dtype=a.dtype)
+    eng = s3.Stage3Engine(cfg, dev, pos_grid=a.pos_grid, dtype=a.dtype, attention=a.attention)
     n_pos = cfg.grid_h * cfg.grid_w if a.pos_grid is None else a.pos_grid ** 2
     eng.load_timm(random_state_dict(a.dim, a.depth, 14, 1 + n_pos, well_conditioned=True))
     g = torch.Generator(device=dev).manual_seed(0)
@@ -79,10 +85,16 @@ def main():
         if mb is None:  # one slicing for both legs: what the larger (bf16) workspace allows
             eng.set_dtype("bfloat16")
             mb = eng.slice_size(a.batch)
-        ms = {"float32": [], "bfloat16": []}
+        modes = {"float32": ("float32", "float32"), "bfloat16": ("bfloat16", "float32"),
+                 "bfloat16_attn": ("bfloat16", "bfloat16")}
+        ms = {name: [] for name in modes}
+        per_image = {}
+        for name, mode in modes.items():
+            eng.set_dtype(*mode)
+            per_image[name] = eng.workspace_bytes(2) - eng.workspace_bytes(1)
         for i in range(a.warmup + a.ab):
-            for dtype in ("float32", "bfloat16"):
-                eng.set_dtype(dtype)
+            for dtype, mode in modes.items():
+                eng.set_dtype(*mode)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 loss = eng.train_step(img, tgt, micro_batch=mb)
@@ -95,10 +107,16 @@ def main():
             v = sorted(v)
             med = v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
             legs[dtype] = {"median_ms": round(med, 2), "min_ms": round(v[0], 2), "max_ms": round(v[-1], 2),
-                           "images_per_s": round(a.batch / med * 1e3, 2), "tflops": round(fl / med / 1e9, 2)}
-        f32, b16 = legs["float32"], legs["bfloat16"]
+                           "images_per_s": round(a.batch / med * 1e3, 2), "tflops": round(fl / med / 1e9, 2),
+                           "workspace_bytes_per_image": per_image[dtype]}
+        f32, b16, att = legs["float32"], legs["bfloat16"], legs["bfloat16_attn"]
         print(json.dumps({**head, "mode": "interleaved_ab", "steps_each": a.ab, "slice": mb, "tflop_per_step": round(fl / 1e12, 2),
-                          "float32": f32, "bfloat16": b16, "speedup": round(f32["median_ms"] / b16["median_ms"], 3),
+                          "float32": f32, "bfloat16": b16, "bfloat16_attn": att,
+                          "speedup": round(f32["median_ms"] / b16["median_ms"], 3),
+                          "attn_speedup_over_bf16": round(b16["median_ms"] / att["median_ms"], 3),
+                          "bf16_spread_ms": round(b16["max_ms"] - b16["min_ms"], 2),
+                          "bf16_attn_faster_than_bf16_spread":
+                              bool(b16["median_ms"] - att["median_ms"] > b16["max_ms"] - b16["min_ms"]),
                           "fp32_spread_ms": round(f32["max_ms"] - f32["min_ms"], 2),
                           "bf16_faster_than_fp32_spread":
                               bool(f32["median_ms"] - b16["median_ms"] > f32["max_ms"] - f32["min_ms"]),
@@ -114,7 +132,7 @@ def main():
         eng.adamw_step(1e-5, 1e-5)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
-    print(json.dumps({**head, "dtype": a.dtype,
+    print(json.dumps({**head, "dtype": a.dtype, "attention": a.attention,
                       "slice": eng.slice_size(a.batch) if mb is None else mb, "ms_per_step": round(dt * 1e3, 2),
                       "images_per_s": round(a.batch / dt, 3), "tflop_per_step": round(fl / 1e12, 2),
                       "tflops": round(fl / dt / 1e12, 2), "fraction_of_fp32_peak": round(fl / dt / PEAK_FP32, 3),
