@@ -50,6 +50,14 @@ int gelu_bwd(const float* h, float* da, int64_t n4, hipStream_t s);
 int loss_rows(bool add, int C, const float* a, const float* b, const float* target, float* out, float* dout, float* acc,
               int n_prefix, int T, int Tp, int R, int norm_batch, float* loss_out, hipStream_t s);
 
+// stage 3's gemm_modes 5 / 7 (dvt_s3_wgrad.hip): dw[n][k] (+)= bf16(dy)^T . bf16(x) from the row casts dyb [R][n], xb [R][k] that the
+// caller made, db[n] (+)= colsum of the fp32 dy; S = dvt_s3_wgrad_splits(R, n, k) or a forced count in 1 .. R / 64; `partial` holds
+// dvt_s3_wgrad_partial_bytes(R, n, k, S) bytes.  R, n, k multiples of 128, everything 16-byte aligned (the caller checks)
+int dvt_s3_wgrad_splits(int64_t R, int n, int k);
+int64_t dvt_s3_wgrad_partial_bytes(int64_t R, int n, int k, int S);
+int dvt_s3_wgrad_bf16_run(const uint16_t* dyb, const uint16_t* xb, const float* dy, float* dw, float* db, void* partial, int64_t R,
+                          int n, int k, int S, int accumulate, hipStream_t s);
+
 // Attention.  q / k / v live in qkv [batch * Tp][3 C] at column offsets 0 / C / 2 C (+ 64 head), P and dP are
 // [batch * heads][Tp][Tp], per-head outputs are 64-column slices of [batch * Tp][C] / [batch * Tp][3 C].
 constexpr int AR_Q = 128;  // s2_attn_rows_kernel walks whole blocks of 128 query rows: rows_kernel needs Tp % AR_Q == 0
@@ -112,6 +120,11 @@ struct BlockBf16 {  // stage 3's gemm_mode 1: the qkv / proj / fc1 / fc2 weights
   // to the bias gradient: the k third of a qkv bias has NO gradient (a softmax row ignores a common shift of its logits), what
   // the rounded dS leaves there is noise, and AdamW would walk the k bias by a learning rate per step on it
   float* qkv_db;
+  // gemm_modes 5 / 7 (xbf non-null): the weight gradients are the bf16 split-K product of dvt_s3_wgrad.hip.  xbf: the layer
+  // input's row cast (abf holds dy's, which the data-gradient GEMM reads at the same time); wpart: the partial tiles, sized for
+  // the largest layer (one of each for all blocks and layers: a layer's backward joins before it returns)
+  uint16_t* xbf;
+  void* wpart;
 };
 struct BlockDims {
   AttnDims ad;
@@ -122,7 +135,7 @@ struct BlockDims {
 // f2 = fc2(gelu(fc1(xn2))) written and NOT added: f1 and f2 are the caller's (a block's own, or one buffer for both where no
 // LayerScale gradient reads them), and the residual add of f2 with the norm behind it is the caller's resid_ln.  block_bwd
 // takes d0 = d(block output), leaves d0 = d xin and uses d1, d2, dh, dqkv, dP, rowdot, wT as scratch.
-// mp null: exact fp32; else forward and data-gradient GEMMs on bf16 operands, weight gradients exact all the same, and with
+// mp null: exact fp32; else forward and data-gradient GEMMs on bf16 operands, weight gradients exact all the same unless mp->xbf, and with
 // mp->aq the flash attention in place of the fp32 products (rows_kernel / fuse_softmax_bwd then choose nothing).
 int block_fwd(const BlockDims& d, const BlockTensors<const float>& p, const BlockActs& k, const BlockBf16* mp, bool rows_kernel,
               hipStream_t s);

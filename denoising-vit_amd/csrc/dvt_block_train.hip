@@ -805,12 +805,21 @@ static int blk_lin_fwd(const BlockBf16* mp, int j, const float* x, const float* 
 }
 
 // dx[R][k] = dy[R][n] . w[n][k];  dw[n][k] += dy^T . x and db[n] += colsum(dy), with mp too in exact fp32 from the UNROUNDED dy
-// and x, on lin_bwd's side stream beside the data gradient as in the fp32 mode
+// and x, on lin_bwd's side stream beside the data gradient as in the fp32 mode -- or, with mp->xbf, dw from the rounded operands
 static int blk_lin_bwd(const BlockBf16* mp, int j, const float* dy, const float* x, const float* w, float* dx, float* dw, float* db,
                        int R, int n, int k, hipStream_t s, float* wT) {
   if (!mp) return lin_bwd(dy, x, w, dx, dw, db, R, n, k, s, wT);
   if (!mp_shape_ok(R, k, n)) return DVT_E_BADARG;
   BlockFork f(s);
+  if (mp->xbf) {  // gemm_modes 5 / 7: dw from the rounded dy and x.  The side stream starts behind dy's cast, which both products read
+    if (k % 128) return DVT_E_BADARG;
+    DVT_TRY(dvt_s3_cast_bf16(dy, mp->abf, R, n, s));
+    DVT_TRY(f.fork());
+    DVT_TRY(dvt_s3_cast_bf16(x, mp->xbf, R, k, f.side()));
+    DVT_TRY(dvt_s3_wgrad_bf16_run(mp->abf, mp->xbf, dy, dw, db, mp->wpart, R, n, k, dvt_s3_wgrad_splits(R, n, k), 1, f.side()));
+    DVT_TRY(dvt_vit_gemm_f32out(mp->abf, mp->wt[j], nullptr, dx, R, k, n, s));
+    return f.join();
+  }
   DVT_TRY(f.fork());
   DVT_TRY(lin_bwd(dy, x, nullptr, nullptr, dw, db, R, n, k, f.side()));  // no dx: the weight and bias gradients alone, beside
   DVT_TRY(dvt_s3_cast_bf16(dy, mp->abf, R, n, s));

@@ -196,12 +196,14 @@ struct S3Work {
   float *col, *wpad, *dwpad, *emb;
   BlockScratch g;
   float *pos, *dpos, *ptmp;  // the run-grid position table, its gradient and the resample's [g0, gw, dim] intermediate
-  BlockBf16 bf[DVT_VIT_MAX_DEPTH];  // gemm_modes 1, 3: per block the bf16 weight copies, and the one A-operand scratch in each;
-                                    // mode 3: the block's bf16 attention operands and lse too
+  BlockBf16 bf[DVT_VIT_MAX_DEPTH];  // gemm_mode bit 1: per block the bf16 weight copies, and the one A-operand scratch in each;
+                                    // bit 2: the block's bf16 attention operands and lse too; bit 4: the weight gradient's scratch
 };
 
-// gemm_mode (include/dvt_stage3.h) is a bit set: 1 = bf16 GEMMs, 2 = bf16 flash attention, which is built on top of them
-bool mode_ok(int mode) { return mode == 0 || mode == 1 || mode == 3; }
+// gemm_mode (include/dvt_stage3.h) is a bit set: 1 = bf16 GEMMs, 2 = bf16 flash attention and 4 = bf16 weight gradients, which
+// are both built on top of them
+enum { MODE_GEMM = 1, MODE_ATTN = 2, MODE_WGRAD = 4 };
+bool mode_ok(int mode) { return mode == 0 || mode == 1 || mode == 3 || mode == 5 || mode == 7; }
 
 // the table's grid differs from the run's: the step resamples pos_embed on its way in and its gradient on the way out
 bool resamples(const DvtVitConfig* c, int g0) { return g0 > 0 && (g0 != c->grid_h || g0 != c->grid_w); }
@@ -209,10 +211,10 @@ bool resamples(const DvtVitConfig* c, int g0) { return g0 > 0 && (g0 != c->grid_
 int64_t carve(const DvtVitConfig* c, int batch, char* base, S3Work* w, int g0 = 0, int mode = 0) {
   const int64_t R = (int64_t)batch * c->s_pad, C = c->dim, F = c->mlp_dim;
   // mode 3 keeps neither P nor a block's fp32 qkv: every block's qkv is the backward's dqkv scratch, idle during the forward
-  const int64_t PP = mode == 3 ? 0 : (int64_t)batch * c->heads * c->s_pad * c->s_pad;
+  const int64_t PP = (mode & MODE_ATTN) ? 0 : (int64_t)batch * c->heads * c->s_pad * c->s_pad;
   Carver cv{base};
   S3Work t{};
-  for (int b = 0; b < c->depth; ++b) carve_block_acts(cv, &t.blk[b], R, C, F, PP, true, mode != 3);
+  for (int b = 0; b < c->depth; ++b) carve_block_acts(cv, &t.blk[b], R, C, F, PP, true, !(mode & MODE_ATTN));
   t.xl = cv.take(R * C);
   t.xf = cv.take(R * C);
   t.meanf = cv.take(R);
@@ -222,7 +224,7 @@ int64_t carve(const DvtVitConfig* c, int batch, char* base, S3Work* w, int g0 = 
   t.dwpad = cv.take(C * c->k_patch);
   t.emb = cv.take(R * C);
   carve_block_scratch(cv, &t.g, R, C, F, PP, (int64_t)batch * c->heads * c->s_pad);
-  if (mode == 3)
+  if (mode & MODE_ATTN)
     for (int b = 0; b < c->depth; ++b) t.blk[b].qkv = t.g.dqkv;
   if (resamples(c, g0)) {  // behind everything else: the equal-grid workspace is what it always was
     const int64_t n = (int64_t)(c->pos_has_cls + c->grid_h * c->grid_w) * C;
@@ -230,7 +232,7 @@ int64_t carve(const DvtVitConfig* c, int batch, char* base, S3Work* w, int g0 = 
     t.dpos = cv.take(n);
     t.ptmp = cv.take((int64_t)g0 * c->grid_w * C);
   }
-  if (mode >= 1) {  // behind everything else again: the fp32 mode's sizes and carving are what they were
+  if (mode & MODE_GEMM) {  // behind everything else again: the fp32 mode's sizes and carving are what they were
     auto take16 = [&](int64_t halves) { return reinterpret_cast<uint16_t*>(cv.take((halves + 1) / 2)); };
     const int64_t wn[4] = {3 * C * C, C * C, F * C, C * F};
     for (int b = 0; b < c->depth; ++b)
@@ -240,13 +242,24 @@ int64_t carve(const DvtVitConfig* c, int batch, char* base, S3Work* w, int g0 = 
       }
     uint16_t* abf = take16(R * (3 * C > F ? 3 * C : F));  // the widest A operand: a / dh [R, mlp_dim] or dqkv [R, 3 dim]
     for (int b = 0; b < c->depth; ++b) t.bf[b].abf = abf;
-    if (mode == 3) {
+    if (mode & MODE_ATTN) {
       for (int b = 0; b < c->depth; ++b) {
         t.bf[b].aq = take16(3 * R * C);
         t.bf[b].lse = cv.take((int64_t)batch * c->heads * c->s_pad);
       }
       float* qkv_db = cv.take(3 * C);
       for (int b = 0; b < c->depth; ++b) t.bf[b].qkv_db = qkv_db;
+    }
+    if (mode & MODE_WGRAD) {  // behind modes 1 and 3: the widest layer input's row cast, and the largest layer's partial tiles
+      uint16_t* xbf = take16(R * (F > C ? F : C));
+      const int ln[4] = {(int)(3 * C), (int)C, (int)F, (int)C}, lk[4] = {(int)C, (int)C, (int)C, (int)F};
+      int64_t part = 0;
+      for (int i = 0; i < 4; ++i) {
+        const int64_t p = dvt_s3_wgrad_partial_bytes(R, ln[i], lk[i], dvt_s3_wgrad_splits(R, ln[i], lk[i]));
+        part = p > part ? p : part;
+      }
+      void* wpart = cv.take(part / 4);
+      for (int b = 0; b < c->depth; ++b) t.bf[b].xbf = xbf, t.bf[b].wpart = wpart;
     }
   }
   if (w) *w = t;
@@ -263,7 +276,7 @@ int run(const DvtVitConfig* c, const float* params, float* grads, const float* i
   if (!params || !grads || !img || !target || !loss_out || !work || batch < 1 || norm_batch < batch) return DVT_E_BADARG;
   S3Work w;
   if (carve(c, batch, reinterpret_cast<char*>(work), &w, g0, mode) > work_bytes) return DVT_E_BADARG;
-  if (mode >= 1 && (!dvt_aligned16(params) || !dvt_aligned16(work))) return DVT_E_BADARG;  // (the casts move 16-byte pieces)
+  if ((mode & MODE_GEMM) && (!dvt_aligned16(params) || !dvt_aligned16(work))) return DVT_E_BADARG;  // (the casts move 16-byte pieces)
   int64_t po[8 + DVT_S3_TENSORS_PER_BLOCK * DVT_VIT_MAX_DEPTH];
   offsets(c, po, g0);
   const int C = c->dim, F = c->mlp_dim, T = c->n_tokens, Tp = c->s_pad, NB = c->depth;
@@ -271,9 +284,9 @@ int run(const DvtVitConfig* c, const float* params, float* grads, const float* i
   const int R = batch * Tp;
   const BlockDims bd{{batch, c->heads, T, Tp, C}, F, c->ln_eps};
   auto P = [&](int b) { return block_tensors(params, po + BLK0 + DVT_S3_TENSORS_PER_BLOCK * b, true); };
-  auto mp = [&](int b) { return mode >= 1 ? &w.bf[b] : nullptr; };
+  auto mp = [&](int b) { return (mode & MODE_GEMM) ? &w.bf[b] : nullptr; };
   const int64_t normw = po[BLK0 + DVT_S3_TENSORS_PER_BLOCK * NB], normb = po[BLK0 + DVT_S3_TENSORS_PER_BLOCK * NB + 1];
-  if (mode >= 1) {  // the weights of this call, rounded once: `params` changes between steps, and a slice is a step's unit
+  if (mode & MODE_GEMM) {  // the weights of this call, rounded once: `params` changes between steps, and a slice is a step's unit
     const int wn[4] = {3 * C, C, F, C}, wk[4] = {C, C, C, F};
     for (int b = 0; b < NB; ++b) {
       const float* wf[4] = {P(b).qkvw, P(b).projw, P(b).fc1w, P(b).fc2w};

@@ -35,6 +35,7 @@ HIP_SOURCES = [
     "dvt_stage2.hip",
     "dvt_stage3.hip",
     "dvt_s3_cast.hip",
+    "dvt_s3_wgrad.hip",
     "dvt_s3_attn.hip",
     "dvt_seg.hip",
     "dvt_depth.hip",
@@ -225,6 +226,9 @@ _SIGNATURES = {
     "dvt_parts_s3_embed": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dvt_parts_s3_embed_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dvt_parts_s3_im2col": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    # include/dvt_stage3.h: the bf16 split-K weight gradient of gemm_modes 5 / 7, exported for tests
+    "dvt_s3_wgrad_bf16_scratch_bytes": (_L, [_L, _I, _I, _I]),
+    "dvt_s3_wgrad_bf16": (_I, [_P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _I, _P]),
 }
 
 PROBES = {"adam": 0, "vit_gemm": 1, "vit_attn": 2, "fit_gemm": 3, "grid": 4, "fit_rows": 5}

@@ -17,6 +17,8 @@ interpolation tables come from torch itself, once per engine (`pos_tables`).
 operands rounded to bf16; weight gradients, arenas, activations and everything that is not one of those GEMMs stay fp32.
 `attention="bfloat16"` on top of it (gemm_mode 3; refused with dtype="float32") runs the blocks' attention as the bf16 flash
 attention of csrc/dvt_s3_attn.hip: no probabilities are kept, so the workspace per image shrinks and `slice_size` grows.
+`weight_grad="bfloat16"` on top of dtype="bfloat16" (gemm_mode bit 4: modes 5 and 7; refused with dtype="float32") forms the
+blocks' weight gradients dW = bf16(dy)^T bf16(x) on the bf16 split-K kernel of csrc/dvt_s3_wgrad.hip; bias gradients stay fp32.
 """
 from __future__ import annotations
 
@@ -54,9 +56,11 @@ _lib.register_signatures({
     "dvt_s3_attn_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
 })
 
-# gemm_mode of dvt_s3_train_slice_pos_mp is a bit set: Stage3Engine(dtype=) gives bit 0, Stage3Engine(attention=) bit 1
+# gemm_mode of dvt_s3_train_slice_pos_mp is a bit set: Stage3Engine(dtype=) gives bit 0, Stage3Engine(attention=) bit 1,
+# Stage3Engine(weight_grad=) bit 2
 GEMM_MODES = {"float32": 0, "bfloat16": 1}
 ATTENTION_MODES = {"float32": 0, "bfloat16": 2}
+WEIGHT_GRAD_MODES = {"float32": 0, "bfloat16": 4}
 ATTENTION_NEEDS_BF16 = ('attention="bfloat16" is built on the bf16 GEMM mode: it needs dtype="bfloat16" '
                         "(--attention bfloat16 needs --dtype bfloat16)")
 
@@ -86,6 +90,33 @@ def attn_bwd(qkvb: torch.Tensor, ao: torch.Tensor, dao: torch.Tensor, lse: torch
     _lib.check(_lib.lib().dvt_s3_attn_bwd(_lib.ptr(qkvb), _lib.ptr(ao), _lib.ptr(dao), _lib.ptr(lse), _lib.ptr(D), _lib.ptr(dqkv),
                                           batch, heads, n_valid, Tp, _lib.stream()), "dvt_s3_attn_bwd")
     return dqkv
+
+
+WEIGHT_GRAD_NEEDS_BF16 = ('weight_grad="bfloat16" is built on the bf16 GEMM mode: it needs dtype="bfloat16" '
+                          "(--weight_grad bfloat16 needs --dtype bfloat16)")
+
+
+def wgrad_bf16(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor | None = None, db: torch.Tensor | None = None,
+               splits: int = 0):
+    """dvt_s3_wgrad_bf16 on its own: dy fp32 [R, n], x fp32 [R, k] (device; R, n, k multiples of 128) -> (dw [n, k], db [n]) with
+    dw = bf16(dy)^T bf16(x) in fp32 accumulation and db = colsum(dy) unrounded.  Given dw / db are ADDED to (accumulate = 1, both
+    or neither); `splits`: 0 = the kernel's own split of the rows, >= 1 forces that many chunks."""
+    _lib.require_cuda(dy, x, dw, db)
+    if (dw is None) != (db is None):
+        raise _lib.DvtError("wgrad_bf16 accumulates into both dw and db or into neither")
+    R, n, k = dy.shape[0], dy.shape[1], x.shape[1]
+    L = _lib.lib()
+    nbytes = int(L.dvt_s3_wgrad_bf16_scratch_bytes(R, n, k, splits))
+    if nbytes < 0 or x.shape[0] != R:
+        raise _lib.DvtError(f"dvt_s3_wgrad_bf16: invalid shape R={R} n={n} k={k} splits={splits}")
+    acc = dw is not None
+    if not acc:
+        dw = torch.empty(n, k, device=dy.device, dtype=torch.float32)
+        db = torch.empty(n, device=dy.device, dtype=torch.float32)
+    scratch = torch.empty(nbytes, device=dy.device, dtype=torch.uint8)
+    _lib.check(L.dvt_s3_wgrad_bf16(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(scratch), nbytes, R, n, k,
+                                   splits, int(acc), _lib.stream()), "dvt_s3_wgrad_bf16")
+    return dw, db
 
 
 def cast_bf16(x: torch.Tensor) -> torch.Tensor:
@@ -189,7 +220,8 @@ def param_layout(cfg: VitConfig, pos_grid: int | None = None):
 
 class Stage3Engine(FlatAdamW):
     def __init__(self, cfg: VitConfig, device: torch.device, pos_grid: int | None = None,
-                 max_work_bytes: int | None = None, dtype: str = "float32", attention: str = "float32"):
+                 max_work_bytes: int | None = None, dtype: str = "float32", attention: str = "float32",
+                 weight_grad: str = "float32"):
         """`pos_grid`: the grid g0 of the checkpoint's position table when `pos_embed` is to keep its [1, cls + g0 g0, dim]
         shape and be resampled to the run's grid in every step; None: the table is at the run's grid (the layout and the
         calls without a resample).
@@ -198,8 +230,10 @@ class Stage3Engine(FlatAdamW):
         `dtype`: "float32" (exact fp32, the default) or "bfloat16": bf16 operands in the forward and data-gradient GEMMs of
         the blocks' linear layers (see the module's docstring); the arenas and the checkpoint are fp32 either way.
         `attention`: "float32" (the default: fp32 products, probabilities kept) or, with dtype="bfloat16" only, "bfloat16":
-        the blocks' attention as bf16 flash attention, which keeps a log-sum-exp per row instead of the probabilities."""
-        self.set_dtype(dtype, attention)
+        the blocks' attention as bf16 flash attention, which keeps a log-sum-exp per row instead of the probabilities.
+        `weight_grad`: "float32" (the default: exact fp32 weight gradients) or, with dtype="bfloat16" only, "bfloat16": the
+        blocks' weight gradients from bf16-rounded dy and x on the split-K kernel; bias gradients stay fp32."""
+        self.set_dtype(dtype, attention, weight_grad)
         if torch.device(device).type != "cuda":
             raise _lib.DvtError("the stage-3 engine needs a HIP device; there is no CPU fallback")
         self.cfg = cfg
@@ -213,18 +247,24 @@ class Stage3Engine(FlatAdamW):
         self._slice_loss = torch.zeros(4, device=self.device, dtype=torch.float32)
         self.max_work_bytes = max_work_bytes
 
-    def set_dtype(self, dtype: str, attention: str = "float32") -> None:
+    def set_dtype(self, dtype: str, attention: str = "float32", weight_grad: str = "float32") -> None:
         """Arithmetic of the following steps.  The state is fp32 either way, so the dtype may change between steps (the
         interleaved A/B of tools/bench_stage3.py does); the workspace grows on demand."""
         if dtype not in GEMM_MODES:
             raise _lib.DvtError(f"the stage-3 step computes in {sorted(GEMM_MODES)}, got dtype={dtype!r}")
         if attention not in ATTENTION_MODES:
             raise _lib.DvtError(f"the stage-3 attention computes in {sorted(ATTENTION_MODES)}, got attention={attention!r}")
+        if weight_grad not in WEIGHT_GRAD_MODES:
+            raise _lib.DvtError(f"the stage-3 weight gradients compute in {sorted(WEIGHT_GRAD_MODES)}, got "
+                                f"weight_grad={weight_grad!r}")
         if attention == "bfloat16" and dtype != "bfloat16":
             raise _lib.DvtError(ATTENTION_NEEDS_BF16)
+        if weight_grad == "bfloat16" and dtype != "bfloat16":
+            raise _lib.DvtError(WEIGHT_GRAD_NEEDS_BF16)
         self.dtype = dtype
         self.attention = attention
-        self.gemm_mode = GEMM_MODES[dtype] | ATTENTION_MODES[attention]
+        self.weight_grad = weight_grad
+        self.gemm_mode = GEMM_MODES[dtype] | ATTENTION_MODES[attention] | WEIGHT_GRAD_MODES[weight_grad]
 
     # ---- parameters -------------------------------------------------------------------------------
     def load_timm(self, state: dict) -> None:

@@ -31,7 +31,8 @@ Deviations, all forced or harmless:
   * `--dtype bfloat16` (default float32, what the reference trains in) is an opt-in mixed-precision student step: see
     dvt_amd/s3.py and include/dvt_stage3.h.  Parameters, optimizer state and checkpoints are fp32 either way, so a
     checkpoint written under one dtype starts a run under the other through `--vit_checkpoint`.  `--attention bfloat16`
-    (default float32) adds the bf16 flash attention on top of `--dtype bfloat16` and is refused without it.
+    (default float32) adds the bf16 flash attention on top of `--dtype bfloat16` and is refused without it; so is
+    `--weight_grad bfloat16` (default float32), which forms the blocks' weight gradients from bf16 operands.
   * the ViT weights come from `--vit_checkpoint` (a timm-layout state dict, or a stage-3 checkpoint) because timm cannot
     download here; `--allow_random_vit` runs on random weights (tests and plumbing only).
 """
@@ -255,10 +256,17 @@ def get_args(argv=None):
                         "(needs --dtype bfloat16): bf16 flash attention -- q, k, v, P, dS and d ao are rounded to bf16 as "
                         "matrix operands, accumulation in fp32; the backward recomputes the probabilities from a per-row "
                         "log-sum-exp, so no [tokens, tokens] matrix is kept and larger slices fit")
+    p.add_argument("--weight_grad", default="float32", choices=["float32", "bfloat16"],
+                   help="float32 (default): the blocks' weight gradients in exact fp32.  bfloat16 (needs --dtype bfloat16): "
+                        "dW = bf16(dy)^T bf16(x) on the bf16 split-K kernel, fp32 accumulation; bias gradients, the patch "
+                        "embedding's gradient, parameters, optimizer state and checkpoints stay fp32")
     args = p.parse_args(argv)
     if args.attention == "bfloat16" and args.dtype != "bfloat16":
         from .s3 import ATTENTION_NEEDS_BF16
         raise SystemExit("stage 3: " + ATTENTION_NEEDS_BF16)
+    if args.weight_grad == "bfloat16" and args.dtype != "bfloat16":
+        from .s3 import WEIGHT_GRAD_NEEDS_BF16
+        raise SystemExit("stage 3: " + WEIGHT_GRAD_NEEDS_BF16)
     if isinstance(args.input_size, int):
         args.input_size = (args.input_size, args.input_size)
     elif len(args.input_size) == 1:
@@ -340,7 +348,8 @@ def build_models(args, device):
     if pos_grid is not None:
         print(f"stage 3: position table {g0} x {g0} resampled to {gh} x {gw} in every step", flush=True)
     student = Stage3Engine(make_config(dim, depth, patch, args.stride_size, *args.input_size, n_reg), device,
-                           pos_grid=pos_grid, dtype=args.dtype, attention=args.attention)
+                           pos_grid=pos_grid, dtype=args.dtype, attention=args.attention,
+                           weight_grad=getattr(args, "weight_grad", "float32"))
     student.load_timm(vit._state_dict)
     return student, teacher
 
@@ -365,6 +374,9 @@ def train(args, rank: int, world: int, device: torch.device, model_factory=None)
         print(f"stage 3: student attention {args.attention}"
               + (" (bf16 flash attention: fp32 accumulation, probabilities recomputed in the backward pass, none kept)"
                  if args.attention == "bfloat16" else " (fp32 products, probabilities kept)"), flush=True)
+        if getattr(args, "weight_grad", "float32") == "bfloat16":
+            print("stage 3: student weight gradients bfloat16 (bf16 operands on the split-K kernel, fp32 accumulation; bias "
+                  "gradients fp32)", flush=True)
     misc.fix_random_seeds(args.seed)
     eng, teacher = (model_factory or build_models)(args, device)
     if distributed:  # DistributedDataParallel broadcasts rank 0's parameters at construction

@@ -35,6 +35,15 @@
  * bf16 operands more).  Everything else -- the teacher, parameters, gradients, AdamW state, checkpoints, LayerNorm,
  * LayerScale, GELU, the loss, the weight gradients, the patch embedding and the position resample -- is as in mode 1.
  *
+ * gemm_modes 5 and 7 (bit 4 on top of mode 1 resp. 3: bf16 weight gradients) form the weight gradient of a block's four linear
+ * layers as dW[n][k] += sum_r bf16(dy[r][n]) bf16(x[r][k]) on v_mfma_f32_32x32x16_bf16 with fp32 accumulation
+ * (csrc/dvt_s3_wgrad.hip): dy's rounding is the one the data gradient of the same layer already uses, x is rounded by one more row
+ * cast.  The reduction over the token rows is split into S chunks of whole 64-row steps, each (128 x 128 tile, chunk) workgroup
+ * writes an fp32 partial tile and a second pass adds the S partials in ascending chunk order into dW: no float atomics, two runs
+ * give the same bits.  S = min(ceil(1024 / tiles), R / 256), at least 1, tiles = (n / 128) (k / 128): a function of (R, n, k) alone.
+ * What stays fp32: every bias gradient db = colsum(dy) from the unrounded dy (mode 7 drops the k third of the qkv bias gradient
+ * exactly as mode 3), the patch embedding's weight gradient (k_patch is not on the 128 grid), and everything modes 1 and 3 keep.
+ *
  * Conventions as in dvt_hip.h: int return codes (0 = ok, DVT_E_* / hipError_t otherwise), device pointers owned by the
  * caller, `stream` is a hipStream_t, nothing synchronises.
  */
@@ -123,13 +132,18 @@ int dvt_s3_train_slice_pos(const DvtVitConfig* cfg, int g0, const float* wy, con
  *            3 = mode 1 and the bf16 flash attention (its workspace: mode 1's less every block's P, the dP scratch and every
  *                block's fp32 qkv, plus 6 dim + 4 heads bytes per token row and block and 12 dim bytes).  The value is a bit set -- 1: the bf16
  *                GEMMs, 2: the bf16 attention -- and the attention is built on the GEMM mode: 2 alone is refused.
+ *            5 = mode 1 and 7 = mode 3 with bit 4, the bf16 split-K weight gradients; built on the GEMM mode too: 4 and 6 are
+ *                refused.  Their workspace is mode 1's resp. 3's, byte for byte, and BEHIND it two pieces (each rounded up to 256
+ *                bytes): 2 max(mlp_dim, dim) bytes per token row (the layer input's row cast) and the partial tiles of the
+ *                largest layer, max over qkv / proj / fc1 / fc2 of dvt_s3_wgrad_bf16_scratch_bytes' last two terms below,
+ *                4 S n k + 4 Sb n bytes, one buffer for all layers and blocks.
  * Modes 1 and 3 round the four weights of every block once per call into the workspace (as stored for the forward, transposed for
  * the data gradient: params change between steps, and each slice rounds the same weights, so slices stay additive) and each
  * A operand into one shared scratch right before its GEMM; the workspace grows by 4 bytes per block weight and
  * 2 max(mlp_dim, 3 dim) bytes per token row, behind mode 0's carving.  g0 as for the _pos calls, or 0: the table is at the
  * run's grid, the layout of dvt_s3_param_offsets and the step of dvt_s3_train_slice (wy, wx ignored).  DVT_E_BADARG (-1 for the
  * size) before any launch: another gemm_mode, g0 < 0, a workspace below the mode's
- * size, a null pointer, in modes 1 and 3 `params` or `work` not 16-byte aligned. */
+ * size, a null pointer, in modes 1, 3, 5 and 7 `params` or `work` not 16-byte aligned. */
 int64_t dvt_s3_workspace_bytes_mp(const DvtVitConfig* cfg, int batch, int g0, int gemm_mode);
 int dvt_s3_train_slice_pos_mp(const DvtVitConfig* cfg, int g0, const float* wy, const float* wx, int gemm_mode,
                               const float* params, float* grads, const float* img, const float* target, float* feat_out,
@@ -142,6 +156,18 @@ int dvt_s3_train_slice_pos_mp(const DvtVitConfig* cfg, int g0, const float* wy, 
  * Pointers 16-byte aligned; DVT_E_BADARG otherwise, nothing launched. */
 int dvt_s3_cast_bf16(const float* x, void* y, int64_t rows, int n, void* stream);
 int dvt_s3_cast_bf16_t(const float* w, void* wt, int n, int k, void* stream);
+
+/* The weight gradient of gemm_modes 5 and 7, exported for tests (csrc/dvt_s3_wgrad.hip):
+ *   dw[n][k] (+)= sum_r bf16(dy[r][n]) bf16(x[r][k]) (fp32 accumulation),  db[n] (+)= sum_r dy[r][n] (dy unrounded)
+ * dy fp32 [R, n], x fp32 [R, k]; R, n, k multiples of 128.  splits: 0 = the rule of "Arithmetic" above, >= 1 forces S (clamped
+ * to the R / 64 row steps).  accumulate: 0 overwrites dw and db, 1 adds to them.  The call rounds dy and x into `scratch`
+ * (dvt_s3_cast_bf16) itself.  scratch bytes, each term rounded up to 256: 2 R n + 2 R k + 4 S n k + 4 Sb n with Sb = clamp(R /
+ * 1024, 1, 128) chunks of the column sum.  No float atomics: two runs give the same bits.
+ * DVT_E_BADARG (-1 for the size), nothing launched: a null pointer, a shape off that grid, dy / x / dw / db / scratch not
+ * 16-byte aligned, scratch_bytes below the size, splits < 0. */
+int64_t dvt_s3_wgrad_bf16_scratch_bytes(int64_t R, int n, int k, int splits);
+int dvt_s3_wgrad_bf16(const float* dy, const float* x, float* dw, float* db, void* scratch, int64_t scratch_bytes, int64_t R, int n,
+                      int k, int splits, int accumulate, void* stream);
 
 /* gemm_mode 3's attention, exported for tests (csrc/dvt_s3_attn.hip).  Head dimension 64, C = 64 heads, R = batch Tp token rows
  * of which the first T of every image are valid; keys >= T are masked.  No float atomics: two runs give the same bits.

@@ -1,6 +1,7 @@
 """Time the stage-3 student step (csrc/dvt_stage3.hip): forward + loss + backward + AdamW of a whole ViT, in exact fp32 or
 in the opt-in bf16 mode (`--dtype bfloat16`: bf16 operands in the forward and data-gradient GEMMs of the linear layers), with
-`--attention bfloat16` on top of it the bf16 flash attention (no probabilities kept).
+`--attention bfloat16` on top of it the bf16 flash attention (no probabilities kept) and with `--weight_grad bfloat16` the bf16
+split-K weight gradients.
 
 Prints one JSON line: ms per step, images/s, and the step's matrix FLOPs per second against the 157 TF/s fp32 MFMA peak
 of the MI355X.  The FLOPs count the student only (forward 1x, backward 2x; tokens padded to s_pad rows as the kernels
@@ -9,7 +10,7 @@ student's step) is not part of the timed step.
 
     python tools/bench_stage3.py [--dim 768 --depth 12 --img 518 --batch 64 --steps 3 --warmup 1]
                                  [--input_size H W] [--stride_size S] [--pos_grid G0]
-                                 [--dtype float32|bfloat16] [--attention float32|bfloat16] [--ab N]
+                                 [--dtype float32|bfloat16] [--attention float32|bfloat16] [--weight_grad float32|bfloat16] [--ab N]
 
 `--ab N`: an interleaved A/B of the three arithmetics in one process on one engine -- fp32 step, bf16 step, bf16 step with
 bf16 attention, fp32 step, ... N of each after the warm-up of all, every step timed on its own (device synchronised on both
@@ -18,7 +19,8 @@ drifts over a run, so two runs one after the other do not compare; alternating s
 carries per leg the median, minimum and maximum ms per step and the workspace bytes per image of its mode (the increment of
 the workspace from one image to two), `bf16_faster_than_fp32_spread`: whether the bf16 median lies below the fp32 median by
 more than the fp32 leg's own min-max spread, and `bf16_attn_faster_than_bf16_spread`: the same for the attention leg against
-the bf16 leg.  All legs run the same slicing: the one the largest workspace (bf16, fp32 attention) allows.
+the bf16 leg.  A fourth leg, `bfloat16_attn_wgrad` (gemm_mode 7: the attention leg plus the bf16 weight gradients), is interleaved
+with the others; `wgrad_faster_than_bf16_attn_spread` compares it with the attention leg in the same way.  All legs run the same slicing: the one the largest workspace (bf16, fp32 attention) allows.
 
 `--input_size` / `--stride_size` set another geometry than `--img` square at stride 14; `--pos_grid G0` keeps the position
 table at G0 x G0 (37 for the DINOv2 checkpoints) and resamples it to the run's grid in every step, e.g.
@@ -63,6 +65,7 @@ def main():
     p.add_argument("--stride_size", type=int, default=14)
     p.add_argument("--dtype", default="float32", choices=["float32", "bfloat16"])
     p.add_argument("--attention", default="float32", choices=["float32", "bfloat16"], help="bfloat16 needs --dtype bfloat16")
+    p.add_argument("--weight_grad", default="float32", choices=["float32", "bfloat16"], help="bfloat16 needs --dtype bfloat16")
     p.add_argument("--ab", type=int, default=0, metavar="N",
                    help="interleaved fp32 / bf16 / bf16 + bf16 attention A/B, N timed steps of each")
     p.add_argument("--pos_grid", type=int, default=None,
@@ -71,7 +74,7 @@ def main():
     dev = torch.device("cuda:0")
     H, W = a.input_size or (a.img, a.img)
     cfg = s3.make_config(a.dim, a.depth, 14, a.stride_size, H, W)
-    eng = s3.Stage3Engine(cfg, dev, pos_grid=a.pos_grid, dtype=a.dtype, attention=a.attention)
+    eng = s3.Stage3Engine(cfg, dev, pos_grid=a.pos_grid, dtype=a.dtype, attention=a.attention, weight_grad=a.weight_grad)
     n_pos = cfg.grid_h * cfg.grid_w if a.pos_grid is None else a.pos_grid ** 2
     eng.load_timm(random_state_dict(a.dim, a.depth, 14, 1 + n_pos, well_conditioned=True))
     g = torch.Generator(device=dev).manual_seed(0)
@@ -86,7 +89,7 @@ def main():
             eng.set_dtype("bfloat16")
             mb = eng.slice_size(a.batch)
         modes = {"float32": ("float32", "float32"), "bfloat16": ("bfloat16", "float32"),
-                 "bfloat16_attn": ("bfloat16", "bfloat16")}
+                 "bfloat16_attn": ("bfloat16", "bfloat16"), "bfloat16_attn_wgrad": ("bfloat16", "bfloat16", "bfloat16")}
         ms = {name: [] for name in modes}
         per_image = {}
         for name, mode in modes.items():
@@ -109,9 +112,13 @@ def main():
             legs[dtype] = {"median_ms": round(med, 2), "min_ms": round(v[0], 2), "max_ms": round(v[-1], 2),
                            "images_per_s": round(a.batch / med * 1e3, 2), "tflops": round(fl / med / 1e9, 2),
                            "workspace_bytes_per_image": per_image[dtype]}
-        f32, b16, att = legs["float32"], legs["bfloat16"], legs["bfloat16_attn"]
+        f32, b16, att, wg = legs["float32"], legs["bfloat16"], legs["bfloat16_attn"], legs["bfloat16_attn_wgrad"]
         print(json.dumps({**head, "mode": "interleaved_ab", "steps_each": a.ab, "slice": mb, "tflop_per_step": round(fl / 1e12, 2),
-                          "float32": f32, "bfloat16": b16, "bfloat16_attn": att,
+                          "float32": f32, "bfloat16": b16, "bfloat16_attn": att, "bfloat16_attn_wgrad": wg,
+                          "wgrad_speedup_over_bf16_attn": round(att["median_ms"] / wg["median_ms"], 3),
+                          "bf16_attn_spread_ms": round(att["max_ms"] - att["min_ms"], 2),
+                          "wgrad_faster_than_bf16_attn_spread":
+                              bool(att["median_ms"] - wg["median_ms"] > att["max_ms"] - att["min_ms"]),
                           "speedup": round(f32["median_ms"] / b16["median_ms"], 3),
                           "attn_speedup_over_bf16": round(b16["median_ms"] / att["median_ms"], 3),
                           "bf16_spread_ms": round(b16["max_ms"] - b16["min_ms"], 2),
@@ -132,7 +139,7 @@ def main():
         eng.adamw_step(1e-5, 1e-5)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
-    print(json.dumps({**head, "dtype": a.dtype, "attention": a.attention,
+    print(json.dumps({**head, "dtype": a.dtype, "attention": a.attention, "weight_grad": a.weight_grad,
                       "slice": eng.slice_size(a.batch) if mb is None else mb, "ms_per_step": round(dt * 1e3, 2),
                       "images_per_s": round(a.batch / dt, 3), "tflop_per_step": round(fl / 1e12, 2),
                       "tflops": round(fl / dt / 1e12, 2), "fraction_of_fp32_peak": round(fl / dt / PEAK_FP32, 3),

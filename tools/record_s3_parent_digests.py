@@ -2,7 +2,7 @@
 tests/golden/s3_parent_digests.json, which `test_default_path_keeps_the_parents_bits` of tests/test_gpu_stage3_bf16.py holds
 every later build to -- through `dvt_s3_train_step` and through `dvt_s3_train_slice_pos_mp` with gemm_mode 0.
 
-    python tools/record_s3_parent_digests.py [--tree PATH_OF_ANOTHER_CHECKOUT] [--out FILE] [--repeat N] [--bf16]
+    python tools/record_s3_parent_digests.py [--tree PATH_OF_ANOTHER_CHECKOUT] [--out FILE] [--repeat N] [--bf16 [--attention]]
 
 `--tree`: import dvt_amd from another checkout of the project (its library built): the parent commit of a change that must
 not alter these bits.  Needs an MI355X; digests are specific to the GPU architecture and the compiler.
@@ -17,6 +17,10 @@ gradient tensor must come out with the same bits in every repeat and is recorded
 s384x2, into tests/golden/s3_bf16_parent_digests.json, which `test_bf16_path_keeps_the_parents_bits` holds.  Same rule, except
 that a tensor `is_atomic` does not name whose bits moved between the repeats is recorded under "varies" too and listed under
 "observed", as tools/record_s2_parent_digests.py does, instead of stopping the recorder.
+
+`--bf16 --attention`: the same for the bf16 flash attention on top (route "mp3": gemm_mode 3 through
+`Stage3Engine(dtype="bfloat16", attention="bfloat16")`) into tests/golden/s3_bf16_attn_parent_digests.json, which
+`test_bf16_attention_path_keeps_the_parents_bits` of tests/test_gpu_stage3_wgrad.py holds.
 """
 import argparse
 import ctypes as C
@@ -49,12 +53,12 @@ def problem(torch, dim, depth, seed=0):
 def step_tensors(torch, case: str, route: str = "step") -> dict:
     """{"loss", "grads.<name>"...} (CPU) of one step of a fresh fp32 engine.  route "step": `dvt_s3_train_step` (what
     Stage3Engine.train_step calls for a whole batch); "mp0": `dvt_s3_train_slice_pos_mp` with g0 = 0 and gemm_mode 0; "mp1":
-    the bf16 engine's train_step, the same entry point with gemm_mode 1."""
+    the bf16 engine's train_step, the same entry point with gemm_mode 1; "mp3": with the bf16 attention too, gemm_mode 3."""
     from dvt_amd import _lib, s3
     dim, depth = CASES[case]
     sd, x, t = problem(torch, dim, depth)
     eng = s3.Stage3Engine(s3.make_config(dim, depth, 14, 14, IMG, IMG), torch.device(DEV),
-                          dtype="bfloat16" if route == "mp1" else "float32")
+                          **({"mp1": dict(dtype="bfloat16"), "mp3": dict(dtype="bfloat16", attention="bfloat16")}.get(route, {})))
     eng.load_timm(sd)
     x, t = x.to(DEV), t.to(DEV)
     if route != "mp0":
@@ -77,8 +81,12 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeat", type=int, default=8)
     ap.add_argument("--bf16", action="store_true")
+    ap.add_argument("--attention", action="store_true", help="with --bf16: the bf16 flash attention too (gemm_mode 3)")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "tests", "golden", "s3_bf16_parent_digests.json" if a.bf16 else "s3_parent_digests.json")
+    if a.attention and not a.bf16:
+        raise SystemExit("--attention records gemm_mode 3, which is built on --bf16")
+    a.out = a.out or os.path.join(ROOT, "tests", "golden", ("s3_bf16_attn_parent_digests.json" if a.attention else
+                                                            "s3_bf16_parent_digests.json") if a.bf16 else "s3_parent_digests.json")
     sys.path.insert(0, os.path.join(os.path.abspath(a.tree), "denoising-vit_amd"))
     import base64
 
@@ -86,7 +94,7 @@ def main():
     H = helpers()
     cases, varies, observed = {}, {}, {}
     for name in (["s384x2"] if a.bf16 else CASES):
-        runs = [step_tensors(torch, name, "mp1" if a.bf16 else "step") for _ in range(max(1, a.repeat))]
+        runs = [step_tensors(torch, name, ("mp3" if a.attention else "mp1") if a.bf16 else "step") for _ in range(max(1, a.repeat))]
         moved = [k for k, v in runs[0].items() if not H.is_atomic(k) and not all(torch.equal(r[k], v) for r in runs)]
         if moved and not a.bf16:
             raise SystemExit(f"{name}: {moved} are not reduced with atomics, yet their bits differ between repeats")
@@ -95,7 +103,7 @@ def main():
         varies[name] = {k: {"shape": list(v.shape), "spread": max(float((r[k] - v).abs().max()) for r in runs),
                             "values": base64.b64encode(v.contiguous().numpy().tobytes()).decode()}
                         for k, v in runs[0].items() if H.is_atomic(k) or k in moved}
-    rec = {"what": ("one train_step of a fresh bf16 Stage3Engine (gemm_mode 1)" if a.bf16 else
+    rec = {"what": (f"one train_step of a fresh bf16 Stage3Engine (gemm_mode {3 if a.attention else 1})" if a.bf16 else
                     "one dvt_s3_train_step of a fresh fp32 Stage3Engine") + ": loss (4 floats) and every gradient tensor; "
                    "problem(dim, depth, 98, 2) of tests/test_gpu_stage3.py at (384, 2) and (768, 1), restated in "
                    "tools/record_s3_parent_digests.py.  cases: sha256 of the fp32 bytes (every repeat gave the same); varies: "
