@@ -156,3 +156,17 @@ struct Carver {
 // likewise (stage 3's gemm_mode 3 points every block's qkv at one scratch buffer)
 void carve_block_acts(Carver& cv, BlockActs* k, int64_t R, int64_t C, int64_t F, int64_t PP, bool own_f, bool own_qkv = true);
 void carve_block_scratch(Carver& cv, BlockScratch* w, int64_t R, int64_t C, int64_t F, int64_t PP, int64_t rowdot_floats);
+
+// ---- gemm_mode of both steps (include/dvt_stage3.h, include/dvt_stage2.h) ----
+// A bit set: 1 = bf16 forward and data-gradient GEMMs, 2 = bf16 flash attention and 4 = bf16 split-K weight gradients, which
+// are both built on top of bit 1
+enum { MODE_GEMM = 1, MODE_ATTN = 2, MODE_WGRAD = 4 };
+inline bool block_mode_ok(int mode) { return mode == 0 || mode == 1 || mode == 3 || mode == 5 || mode == 7; }
+// The mode's pieces of nb blocks, which a step carves behind everything its mode 0 carves (so that mode 0 keeps its sizes):
+// bit 1 every block's w / wt and one abf [R][max(3 C, F)] for all; bit 2 every block's aq [3][R][C] and lse [lse_floats =
+// batch * heads * Tp] and one qkv_db [3 C]; bit 4 one xbf [R][max(F, C)] and one wpart (the largest layer's partial tiles).
+// mode 0: nothing
+void carve_block_bf16(Carver& cv, BlockBf16* bf, int nb, int64_t R, int64_t C, int64_t F, int64_t lse_floats, int mode);
+// One block's four weight matrices of THIS call rounded into bf.w (as they lie, [n, k]) and bf.wt (transposed): `params`
+// changes between steps.  The casts move 16-byte pieces: the caller checks the alignment of its arenas
+int cast_block_weights(const BlockTensors<const float>& p, const BlockBf16& bf, int C, int F, hipStream_t s);

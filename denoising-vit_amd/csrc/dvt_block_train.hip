@@ -432,9 +432,41 @@ __global__ __launch_bounds__(256) void s2_rowdot_kernel(const float* __restrict_
 //   l2 = mean((o - t)^2) over the N C loss elements, N = batch * (T - n_prefix) rows
 //   cos_t = o.t / (max(|o|, 1e-8) max(|t|, 1e-8)) (F.cosine_similarity, eps 1e-8);  loss = l2 + 1 - mean_t cos_t
 //   dout = 2 (o - t) / (N C) - (t / (|o| |t|) - cos o / |o|^2) / N
-// acc[0] += sum (o - t)^2, acc[1] += sum cos (block partials, fp32 atomics).  Prefix and padded rows: dout = 0.
+// The two sums, of (o - t)^2 and of cos, are added over the workgroups' partials in acc as 128-bit fixed-point integers
+// (loss_acc_add below): integer addition does not depend on the order in which the workgroups arrive, so the loss has the same
+// bits on every run of the same input.  Prefix and padded rows: dout = 0.
 // target and out (may be NULL; receives o) are packed [batch, T - n_prefix, C].
 // ==========================================================================================================
+// acc (64 floats, cleared by the caller, 8-byte aligned) as the loss kernels use it: sum i (0: squared error, 1: cosine) is the
+// signed 128-bit integer (hi = u64[2 i + 1], lo = u64[2 i]) in units of 2^-64, floats [8 + i] take what that cannot hold.
+// v, a workgroup's fp32 partial, is exact as a double; floor(v) and v - floor(v) are exact too, the fraction is cut below
+// 2^-64 (a function of v alone).  lo is added with a returning 64-bit atomic and its carry goes into hi: both are additions
+// modulo 2^64 of values that depend on v only, so the final 128 bits are the exact sum of the cut partials in any order.  A
+// partial that is not finite, or at least 2^62 in size, goes to the float slot with a float atomic instead: the loss then
+// comes out non-finite (or huge), which is what the trainers' non-finite check looks for.
+__device__ __forceinline__ void loss_acc_add(float* acc, int i, float v) {
+  if (!(fabsf(v) < 4.6e18f)) {  // (also NaN)
+    atomic_add_f32(acc + 8 + i, v);
+    return;
+  }
+  const double d = (double)v, fl = floor(d);
+  const unsigned long long lo = (unsigned long long)((d - fl) * 18446744073709551616.0);  // < 2^64: the fraction is < 1
+  unsigned long long hi = (unsigned long long)(long long)fl;
+  unsigned long long* w = reinterpret_cast<unsigned long long*>(acc) + 2 * i;
+  if (lo) {
+    const unsigned long long old = __hip_atomic_fetch_add(w, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    hi += (old + lo < old) ? 1ull : 0ull;  // the carry out of the low word
+  }
+  if (hi) __hip_atomic_fetch_add(w + 1, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the sum back as a float: one rounding to double of each word, one of their sum, one to float -- a function of the 128 bits
+__device__ __forceinline__ float loss_acc_get(const float* acc, int i) {
+  const unsigned long long* w = reinterpret_cast<const unsigned long long*>(acc) + 2 * i;
+  const double v = (double)(long long)w[1] + (double)w[0] * (1.0 / 18446744073709551616.0);
+  return (float)v + acc[8 + i];
+}
+
 template <int C, bool ADD>
 __global__ __launch_bounds__(256) void s2_loss_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                       const float* __restrict__ target, float* __restrict__ out,
@@ -492,14 +524,14 @@ __global__ __launch_bounds__(256) void s2_loss_kernel(const float* __restrict__ 
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    atomic_add_f32(acc + 0, (part[0][0] + part[0][1]) + (part[0][2] + part[0][3]));
-    atomic_add_f32(acc + 1, (part[1][0] + part[1][1]) + (part[1][2] + part[1][3]));
+    loss_acc_add(acc, 0, (part[0][0] + part[0][1]) + (part[0][2] + part[0][3]));
+    loss_acc_add(acc, 1, (part[1][0] + part[1][1]) + (part[1][2] + part[1][3]));
   }
 }
 
 // loss_out = {l2 + 1 - cos, l2, 1 - cos, 0} from the two accumulated sums
 __global__ void s2_loss_finish_kernel(const float* __restrict__ acc, float* __restrict__ out, float inv_el, float inv_tok) {
-  const float l2 = acc[0] * inv_el, cl = 1.0f - acc[1] * inv_tok;
+  const float l2 = loss_acc_get(acc, 0) * inv_el, cl = 1.0f - loss_acc_get(acc, 1) * inv_tok;
   out[0] = l2 + cl;
   out[1] = l2;
   out[2] = cl;
@@ -912,6 +944,48 @@ void carve_block_scratch(Carver& cv, BlockScratch* w, int64_t R, int64_t C, int6
   w->rowdot = cv.take(rowdot_floats);            // [batch * heads * Tp] rowsum(dP (.) P) of the softmax backward
 }
 
+void carve_block_bf16(Carver& cv, BlockBf16* bf, int nb, int64_t R, int64_t C, int64_t F, int64_t lse_floats, int mode) {
+  if (!(mode & MODE_GEMM)) return;
+  auto take16 = [&](int64_t halves) { return reinterpret_cast<uint16_t*>(cv.take((halves + 1) / 2)); };
+  const int64_t wn[4] = {3 * C * C, C * C, F * C, C * F};
+  for (int b = 0; b < nb; ++b)
+    for (int i = 0; i < 4; ++i) {
+      bf[b].w[i] = take16(wn[i]);
+      bf[b].wt[i] = take16(wn[i]);
+    }
+  uint16_t* abf = take16(R * (3 * C > F ? 3 * C : F));  // the widest A operand: a / dh [R, mlp_dim] or dqkv [R, 3 dim]
+  for (int b = 0; b < nb; ++b) bf[b].abf = abf;
+  if (mode & MODE_ATTN) {
+    for (int b = 0; b < nb; ++b) {
+      bf[b].aq = take16(3 * R * C);
+      bf[b].lse = cv.take(lse_floats);
+    }
+    float* qkv_db = cv.take(3 * C);
+    for (int b = 0; b < nb; ++b) bf[b].qkv_db = qkv_db;
+  }
+  if (mode & MODE_WGRAD) {  // behind modes 1 and 3: the widest layer input's row cast, and the largest layer's partial tiles
+    uint16_t* xbf = take16(R * (F > C ? F : C));
+    const int ln[4] = {(int)(3 * C), (int)C, (int)F, (int)C}, lk[4] = {(int)C, (int)C, (int)C, (int)F};
+    int64_t part = 0;
+    for (int i = 0; i < 4; ++i) {
+      const int64_t p = dvt_s3_wgrad_partial_bytes(R, ln[i], lk[i], dvt_s3_wgrad_splits(R, ln[i], lk[i]));
+      part = p > part ? p : part;
+    }
+    void* wpart = cv.take(part / 4);
+    for (int b = 0; b < nb; ++b) bf[b].xbf = xbf, bf[b].wpart = wpart;
+  }
+}
+
+int cast_block_weights(const BlockTensors<const float>& p, const BlockBf16& bf, int C, int F, hipStream_t s) {
+  const int wn[4] = {3 * C, C, F, C}, wk[4] = {C, C, C, F};
+  const float* wf[4] = {p.qkvw, p.projw, p.fc1w, p.fc2w};
+  for (int j = 0; j < 4; ++j) {
+    DVT_TRY(dvt_s3_cast_bf16(wf[j], bf.w[j], wn[j], wk[j], s));
+    DVT_TRY(dvt_s3_cast_bf16_t(wf[j], bf.wt[j], wn[j], wk[j], s));
+  }
+  return 0;
+}
+
 // ---- component entry points for tests (include/dvt_parts.h): forwarders to the launchers above; no kernel and no launch of
 // their own, every check in front of the first launch ----
 extern "C" int dvt_parts_lin_fwd(const float* x, const float* w, const float* b, float* y, int R, int n, int k, void* stream) {
@@ -960,6 +1034,7 @@ extern "C" int dvt_parts_gelu(const float* h, float* a, int64_t n4, int backward
 extern "C" int dvt_parts_loss_rows(int C, const float* a, const float* b, const float* target, float* out, float* dout, float* acc,
                                    int n_prefix, int T, int Tp, int R, int norm_batch, float* loss_out, int add, void* stream) {
   if (!parts_c_ok(C) || !a || !target || !dout || !acc || !loss_out || (add && !b) || (add != 0 && add != 1)) return DVT_E_BADARG;
+  if (reinterpret_cast<uintptr_t>(acc) & 7) return DVT_E_BADARG;  // (the loss sums are 64-bit words)
   if (n_prefix < 0 || T <= n_prefix || Tp < T || R < 1 || (R % Tp) || norm_batch < R / Tp) return DVT_E_BADARG;
   return loss_rows(add != 0, C, a, add ? b : nullptr, target, out, dout, acc, n_prefix, T, Tp, R, norm_batch, loss_out,
                    (hipStream_t)stream);

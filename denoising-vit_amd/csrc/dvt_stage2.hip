@@ -188,31 +188,45 @@ struct S2Work {
   BlockActs blk[DVT_S2_MAX_BLOCKS];
   BlockScratch g;  // training; inference with several blocks: d0 alone, the ping-pong partner of blk[0].xin
   float* tmp;      // f1 and f2 of every block: without LayerScale no gradient reads them
+  BlockBf16 bf[DVT_S2_MAX_BLOCKS];  // gemm_mode (include/dvt_stage2.h) != 0: what dvt_block_train.h's carve_block_bf16 lays out
 };
 
-int64_t carve(const DvtS2Config* c, int batch, int training, char* base, S2Work* w) {
+// gemm_mode != 0 (training only): the bf16 kernels walk 128-row tiles of an image's rows and of the mlp columns
+bool mode_shape_ok(const DvtS2Config* c, int mode) { return mode == 0 || (c->tokens_pad % 128 == 0 && c->mlp_dim % 128 == 0); }
+
+int64_t carve(const DvtS2Config* c, int batch, int training, char* base, S2Work* w, int mode = 0) {
   const int64_t R = (int64_t)batch * c->tokens_pad, C = c->dim, F = c->mlp_dim;
-  const int64_t PP = (int64_t)batch * c->heads * c->tokens_pad * c->tokens_pad;
+  // with the flash attention neither P nor dP nor a block's fp32 qkv is kept: every block's qkv is the backward's dqkv
+  // scratch, idle during the forward (as in the stage-3 step)
+  const int64_t PP = (mode & MODE_ATTN) ? 0 : (int64_t)batch * c->heads * c->tokens_pad * c->tokens_pad;
   Carver cv{base};
   S2Work t{};
   const int nb = training ? c->n_blocks : 1;
-  for (int b = 0; b < nb; ++b) carve_block_acts(cv, &t.blk[b], R, C, F, PP, false);
+  for (int b = 0; b < nb; ++b) carve_block_acts(cv, &t.blk[b], R, C, F, PP, false, !(mode & MODE_ATTN));
   for (int b = nb; b < c->n_blocks; ++b) t.blk[b] = t.blk[0];  // inference: every block reuses one set
   if (!training && c->n_blocks > 1) t.g.d0 = cv.take(R * C);   // ping-pong partner of blk[0].xin
   t.tmp = cv.take(R * C);
   if (training) carve_block_scratch(cv, &t.g, R, C, F, PP, (int64_t)batch * c->heads * c->tokens_pad);
   for (int b = 0; b < c->n_blocks; ++b) t.blk[b].f1 = t.blk[b].f2 = t.tmp;
+  if (training) {
+    if (mode & MODE_ATTN)
+      for (int b = 0; b < c->n_blocks; ++b) t.blk[b].qkv = t.g.dqkv;
+    // behind everything else: mode 0's sizes and carving are what they were
+    carve_block_bf16(cv, t.bf, c->n_blocks, R, C, F, (int64_t)batch * c->heads * c->tokens_pad, mode);
+  }
   if (w) *w = t;
   return cv.o;
 }
 
 int run(const DvtS2Config* c, const float* params, float* grads, const float* x, const float* target, float* pred,
-        int batch, void* work, int64_t work_bytes, float* loss_out, hipStream_t s) {
+        int batch, void* work, int64_t work_bytes, float* loss_out, hipStream_t s, int mode = 0) {
   DVT_TRY(check_cfg(c));
   const int training = grads != nullptr;
   if (!params || !x || batch < 1 || !work || (training && (!target || !loss_out)) || (!training && !pred)) return DVT_E_BADARG;
+  if (!block_mode_ok(mode) || (mode && !training) || !mode_shape_ok(c, mode)) return DVT_E_BADARG;
+  if (mode && (!dvt_aligned16(params) || !dvt_aligned16(work))) return DVT_E_BADARG;  // (the casts move 16-byte pieces)
   S2Work w;
-  if (carve(c, batch, training, reinterpret_cast<char*>(work), &w) > work_bytes) return DVT_E_BADARG;
+  if (carve(c, batch, training, reinterpret_cast<char*>(work), &w, mode) > work_bytes) return DVT_E_BADARG;
   S2Offsets po;
   offsets(c, &po);
   const int C = c->dim, T = c->tokens, Tp = c->tokens_pad, NB = c->n_blocks;
@@ -223,6 +237,9 @@ int run(const DvtS2Config* c, const float* params, float* grads, const float* x,
   auto xin = [&](int b) {  // inference with several blocks: block inputs ping-pong
     return training ? w.blk[b].xin : (b & 1) ? w.g.d0 : w.blk[0].xin;
   };
+  auto mp = [&](int b) { return (mode & MODE_GEMM) ? &w.bf[b] : nullptr; };
+  if (mode & MODE_GEMM)  // the weights of this call, rounded once: `params` changes between steps
+    for (int b = 0; b < NB; ++b) DVT_TRY(cast_block_weights(P(b), w.bf[b], C, c->mlp_dim, s));
 
   // ---- forward ----
   DVT_TRY(add_ln(C, x, 1, c->enable_pe ? params + po.pos : nullptr, 1, w.blk[0].xin, P(0).n1w, P(0).n1b, w.blk[0].xn1,
@@ -230,7 +247,7 @@ int run(const DvtS2Config* c, const float* params, float* grads, const float* x,
   for (int b = 0; b < NB; ++b) {
     BlockActs k = w.blk[b];
     k.xin = xin(b);
-    DVT_TRY(block_fwd(bd, P(b), k, nullptr, attn_rows, s));
+    DVT_TRY(block_fwd(bd, P(b), k, mp(b), attn_rows, s));
     if (b + 1 < NB) {
       const BlockActs& n = w.blk[b + 1];
       DVT_TRY(resid_ln(C, k.x1, k.f2, nullptr, xin(b + 1), P(b + 1).n1w, P(b + 1).n1b, n.xn1, n.mean1, n.rstd1, T, Tp, R,
@@ -251,7 +268,7 @@ int run(const DvtS2Config* c, const float* params, float* grads, const float* x,
 
   // ---- backward: d0 holds the gradient w.r.t. the current block's OUTPUT ----
   for (int b = NB - 1; b >= 0; --b)
-    DVT_TRY(block_bwd(bd, P(b), block_tensors(grads, po.t[b], false), w.blk[b], w.g, nullptr, attn_rows,
+    DVT_TRY(block_bwd(bd, P(b), block_tensors(grads, po.t[b], false), w.blk[b], w.g, mp(b), attn_rows,
                       g_s2_fuse_softmax_bwd != 0, s));
   if (c->enable_pe) {
     const int64_t n = (int64_t)T * (C / 4);
@@ -326,6 +343,20 @@ extern "C" int dvt_s2_train_step(const DvtS2Config* cfg, const float* params, fl
   s2_read_env();
   if (!grads) return DVT_E_BADARG;
   return run(cfg, params, grads, x, target, pred, batch, work, work_bytes, loss_out, (hipStream_t)stream);
+}
+
+extern "C" int64_t dvt_s2_workspace_bytes_mp(const DvtS2Config* cfg, int batch, int training, int gemm_mode) {
+  if (check_cfg(cfg) != 0 || batch < 1 || !block_mode_ok(gemm_mode) || !mode_shape_ok(cfg, gemm_mode)) return -1;
+  if (gemm_mode && !training) return -1;  // (bf16 inference is Denoiser(inference_dtype="bfloat16"), not this forward)
+  return carve(cfg, batch, training, nullptr, nullptr, gemm_mode);
+}
+
+extern "C" int dvt_s2_train_step_mp(const DvtS2Config* cfg, const float* params, float* grads, const float* x,
+                                    const float* target, float* pred, int batch, void* work, int64_t work_bytes,
+                                    float* loss_out, void* stream, int gemm_mode) {
+  s2_read_env();
+  if (!grads || !block_mode_ok(gemm_mode)) return DVT_E_BADARG;
+  return run(cfg, params, grads, x, target, pred, batch, work, work_bytes, loss_out, (hipStream_t)stream, gemm_mode);
 }
 
 extern "C" int dvt_adamw_step(float* params, float* grads, float* m, float* v, int64_t n, float lr, float beta1,

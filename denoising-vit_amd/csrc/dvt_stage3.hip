@@ -200,10 +200,8 @@ struct S3Work {
                                     // bit 2: the block's bf16 attention operands and lse too; bit 4: the weight gradient's scratch
 };
 
-// gemm_mode (include/dvt_stage3.h) is a bit set: 1 = bf16 GEMMs, 2 = bf16 flash attention and 4 = bf16 weight gradients, which
-// are both built on top of them
-enum { MODE_GEMM = 1, MODE_ATTN = 2, MODE_WGRAD = 4 };
-bool mode_ok(int mode) { return mode == 0 || mode == 1 || mode == 3 || mode == 5 || mode == 7; }
+// gemm_mode (include/dvt_stage3.h): the bit set MODE_GEMM | MODE_ATTN | MODE_WGRAD of dvt_block_train.h
+bool mode_ok(int mode) { return block_mode_ok(mode); }
 
 // the table's grid differs from the run's: the step resamples pos_embed on its way in and its gradient on the way out
 bool resamples(const DvtVitConfig* c, int g0) { return g0 > 0 && (g0 != c->grid_h || g0 != c->grid_w); }
@@ -232,36 +230,8 @@ int64_t carve(const DvtVitConfig* c, int batch, char* base, S3Work* w, int g0 = 
     t.dpos = cv.take(n);
     t.ptmp = cv.take((int64_t)g0 * c->grid_w * C);
   }
-  if (mode & MODE_GEMM) {  // behind everything else again: the fp32 mode's sizes and carving are what they were
-    auto take16 = [&](int64_t halves) { return reinterpret_cast<uint16_t*>(cv.take((halves + 1) / 2)); };
-    const int64_t wn[4] = {3 * C * C, C * C, F * C, C * F};
-    for (int b = 0; b < c->depth; ++b)
-      for (int i = 0; i < 4; ++i) {
-        t.bf[b].w[i] = take16(wn[i]);
-        t.bf[b].wt[i] = take16(wn[i]);
-      }
-    uint16_t* abf = take16(R * (3 * C > F ? 3 * C : F));  // the widest A operand: a / dh [R, mlp_dim] or dqkv [R, 3 dim]
-    for (int b = 0; b < c->depth; ++b) t.bf[b].abf = abf;
-    if (mode & MODE_ATTN) {
-      for (int b = 0; b < c->depth; ++b) {
-        t.bf[b].aq = take16(3 * R * C);
-        t.bf[b].lse = cv.take((int64_t)batch * c->heads * c->s_pad);
-      }
-      float* qkv_db = cv.take(3 * C);
-      for (int b = 0; b < c->depth; ++b) t.bf[b].qkv_db = qkv_db;
-    }
-    if (mode & MODE_WGRAD) {  // behind modes 1 and 3: the widest layer input's row cast, and the largest layer's partial tiles
-      uint16_t* xbf = take16(R * (F > C ? F : C));
-      const int ln[4] = {(int)(3 * C), (int)C, (int)F, (int)C}, lk[4] = {(int)C, (int)C, (int)C, (int)F};
-      int64_t part = 0;
-      for (int i = 0; i < 4; ++i) {
-        const int64_t p = dvt_s3_wgrad_partial_bytes(R, ln[i], lk[i], dvt_s3_wgrad_splits(R, ln[i], lk[i]));
-        part = p > part ? p : part;
-      }
-      void* wpart = cv.take(part / 4);
-      for (int b = 0; b < c->depth; ++b) t.bf[b].xbf = xbf, t.bf[b].wpart = wpart;
-    }
-  }
+  // behind everything else again: the fp32 mode's sizes and carving are what they were
+  carve_block_bf16(cv, t.bf, c->depth, R, C, F, (int64_t)batch * c->heads * c->s_pad, mode);
   if (w) *w = t;
   return cv.o;
 }
@@ -286,16 +256,8 @@ int run(const DvtVitConfig* c, const float* params, float* grads, const float* i
   auto P = [&](int b) { return block_tensors(params, po + BLK0 + DVT_S3_TENSORS_PER_BLOCK * b, true); };
   auto mp = [&](int b) { return (mode & MODE_GEMM) ? &w.bf[b] : nullptr; };
   const int64_t normw = po[BLK0 + DVT_S3_TENSORS_PER_BLOCK * NB], normb = po[BLK0 + DVT_S3_TENSORS_PER_BLOCK * NB + 1];
-  if (mode & MODE_GEMM) {  // the weights of this call, rounded once: `params` changes between steps, and a slice is a step's unit
-    const int wn[4] = {3 * C, C, F, C}, wk[4] = {C, C, C, F};
-    for (int b = 0; b < NB; ++b) {
-      const float* wf[4] = {P(b).qkvw, P(b).projw, P(b).fc1w, P(b).fc2w};
-      for (int j = 0; j < 4; ++j) {
-        DVT_TRY(dvt_s3_cast_bf16(wf[j], w.bf[b].w[j], wn[j], wk[j], s));
-        DVT_TRY(dvt_s3_cast_bf16_t(wf[j], w.bf[b].wt[j], wn[j], wk[j], s));
-      }
-    }
-  }
+  if (mode & MODE_GEMM)  // the weights of this call, rounded once: `params` changes between steps, and a slice is a step's unit
+    for (int b = 0; b < NB; ++b) DVT_TRY(cast_block_weights(P(b), w.bf[b], C, F, s));
 
   // ---- forward: patch embedding, token assembly, block 0's norm1 ----
   {

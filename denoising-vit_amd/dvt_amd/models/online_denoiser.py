@@ -39,8 +39,13 @@ class Denoiser(nn.Module):
     RESIZED_CACHE = 4  # resized inference copies kept (LRU)
     def __init__(self, noise_map_height: int = 37, noise_map_width: int = 37, feat_dim: int = 768,
                  vit: PretrainedViTWrapper = None, enable_pe: bool = True, num_blocks: int = 1,
-                 device: torch.device | str = "cuda", seed: int | None = None, inference_dtype: str = "float32"):
-        """inference_dtype: arithmetic of `forward`.  "float32" (default): the exact-fp32 forward of the trainer
+                 device: torch.device | str = "cuda", seed: int | None = None, inference_dtype: str = "float32",
+                 train_dtype: str = "float32", train_attention: str = "float32", train_weight_grad: str = "float32"):
+        """train_dtype / train_attention / train_weight_grad: arithmetic of `training_step`, handed to `Stage2Engine` as its
+        dtype / attention / weight_grad ("float32" each by default: exact fp32; "bfloat16" opt-in, the last two on top of
+        train_dtype="bfloat16" only).  `forward`, `load_state_dict`, the state dict and the checkpoint format do not depend on
+        them.
+        inference_dtype: arithmetic of `forward`.  "float32" (default): the exact-fp32 forward of the trainer
         (Stage2Engine.forward).  "bfloat16" (opt-in): the bf16 extractor's block kernels (dvt_amd.denoiser_bf16) -- on the
         given features without a `vit`; with one, image in and denoised features out of one launch sequence, for which the
         wrapper must run in bfloat16 too.  Training and the state dict are fp32 either way."""
@@ -51,11 +56,14 @@ class Denoiser(nn.Module):
             raise ValueError(f"Denoiser(inference_dtype='bfloat16') over a vit with dtype={vit.dtype!r}: the fused forward "
                              "reads the bf16 extractor's residual stream; build the wrapper with dtype='bfloat16' or keep "
                              "inference_dtype='float32'")
+        mode = s2.gemm_mode(train_dtype, train_attention, train_weight_grad)  # (refused by name before a device is touched)
         self.inference_dtype = inference_dtype
         self.vit = vit
         self.noise_map_size = (noise_map_height, noise_map_width)
-        cfg = s2.make_config(feat_dim, noise_map_height * noise_map_width, num_blocks, enable_pe)
-        self.engine = s2.Stage2Engine(cfg, torch.device(device))
+        cfg = s2.make_config(feat_dim, noise_map_height * noise_map_width, num_blocks, enable_pe,
+                             row_pad=s2.BF16_ROW_PAD if mode else 64)
+        self.engine = s2.Stage2Engine(cfg, torch.device(device), dtype=train_dtype, attention=train_attention,
+                                      weight_grad=train_weight_grad)
         g = None if seed is None else torch.Generator().manual_seed(seed)
         self.engine.init_parameters(g)
         # registration order of the reference: denoiser blocks, then pos_embed (online_denoiser.py:24-57)

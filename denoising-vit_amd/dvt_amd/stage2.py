@@ -222,7 +222,25 @@ def get_args(argv=None):
     p.add_argument("--device", default="cuda")
     p.add_argument("--resume", default=None, type=str, help="checkpoint to continue from (not in the reference)")
     p.add_argument("--log_freq", default=50, type=int)
+    p.add_argument("--dtype", default="float32", choices=["float32", "bfloat16"],
+                   help="float32 (default): the training step in exact fp32, as the reference trains.  bfloat16: the forward "
+                        "and data-gradient GEMMs of the blocks' linear layers take bf16 operands (fp32 accumulation); weight "
+                        "gradients, parameters, optimizer state and checkpoints stay fp32")
+    p.add_argument("--attention", default="float32", choices=["float32", "bfloat16"],
+                   help="float32 (default): attention as fp32 products with the probabilities kept.  bfloat16 (needs --dtype "
+                        "bfloat16): bf16 flash attention, fp32 accumulation; the backward recomputes the probabilities from a "
+                        "per-row log-sum-exp, so no [tokens, tokens] matrix is kept")
+    p.add_argument("--weight_grad", default="float32", choices=["float32", "bfloat16"],
+                   help="float32 (default): the blocks' weight gradients in exact fp32.  bfloat16 (needs --dtype bfloat16): "
+                        "dW = bf16(dy)^T bf16(x) on the bf16 split-K kernel, fp32 accumulation; bias and pos_embed gradients, "
+                        "parameters, optimizer state and checkpoints stay fp32")
     args = p.parse_args(argv)
+    if args.attention == "bfloat16" and args.dtype != "bfloat16":
+        from .s2 import ATTENTION_NEEDS_BF16
+        raise SystemExit("stage 2: " + ATTENTION_NEEDS_BF16)
+    if args.weight_grad == "bfloat16" and args.dtype != "bfloat16":
+        from .s2 import WEIGHT_GRAD_NEEDS_BF16
+        raise SystemExit("stage 2: " + WEIGHT_GRAD_NEEDS_BF16)
     if isinstance(args.input_size, int):
         args.input_size = (args.input_size, args.input_size)
     elif len(args.input_size) == 1:
@@ -258,7 +276,13 @@ def train(args, rank: int, world: int, device: torch.device, model_factory=None)
     feat_dim, pos_h, pos_w = model_geometry(args)
     if model_factory is None:
         model = Denoiser(noise_map_height=pos_h, noise_map_width=pos_w, feat_dim=feat_dim, vit=None,
-                         num_blocks=args.num_blocks, device=device)
+                         num_blocks=args.num_blocks, device=device, train_dtype=getattr(args, "dtype", "float32"),
+                         train_attention=getattr(args, "attention", "float32"),
+                         train_weight_grad=getattr(args, "weight_grad", "float32"))
+        if rank == 0:
+            print(f"stage 2: training step dtype {model.engine.dtype}, attention {model.engine.attention}, weight gradients "
+                  f"{model.engine.weight_grad} (gemm_mode {model.engine.gemm_mode}; parameters, optimizer state and "
+                  "checkpoints fp32)", flush=True)
     else:
         model = model_factory(pos_h, pos_w, feat_dim, args.num_blocks, device)
     eng = model.engine

@@ -260,6 +260,11 @@ def get_args(argv=None):
                    help="float32 (default): the blocks' weight gradients in exact fp32.  bfloat16 (needs --dtype bfloat16): "
                         "dW = bf16(dy)^T bf16(x) on the bf16 split-K kernel, fp32 accumulation; bias gradients, the patch "
                         "embedding's gradient, parameters, optimizer state and checkpoints stay fp32")
+    p.add_argument("--teacher_dtype", default="float32", choices=["float32", "bfloat16"],
+                   help="float32 (default): the teacher -- the ViT extractor and the stage-2 denoiser over it -- in exact fp32.  "
+                        "bfloat16: the teacher's forward on the bf16 extractor with the denoiser's block fused behind it (one "
+                        "launch sequence from image to denoised features); the student, its weights and every student mode "
+                        "do not depend on it")
     args = p.parse_args(argv)
     if args.attention == "bfloat16" and args.dtype != "bfloat16":
         from .s3 import ATTENTION_NEEDS_BF16
@@ -331,16 +336,22 @@ def teacher_grid(den_sd: dict, dim: int, gh: int, gw: int) -> tuple:
 
 def build_models(args, device):
     """-> (student engine, teacher).  The teacher is `Denoiser(vit=PretrainedViTWrapper(..., dtype="float32"))` with the
-    stage-2 checkpoint loaded non-strictly (main_distillation.py:131-141); the student starts from the same ViT weights."""
+    stage-2 checkpoint loaded non-strictly (main_distillation.py:131-141); the student starts from the same ViT weights.
+    --teacher_dtype bfloat16 builds the wrapper with dtype="bfloat16" and the Denoiser with inference_dtype="bfloat16" (the
+    fused bf16 forward); the student is loaded from the wrapper's fp32 `_state_dict` either way."""
     from .models.online_denoiser import Denoiser
     from .models.vit_wrapper import PretrainedViTWrapper
     from .s3 import Stage3Engine, make_config
     dim, depth, patch, gh, gw, n_reg = geometry(args)
+    teacher_dtype = getattr(args, "teacher_dtype", "float32")
+    if teacher_dtype not in ("float32", "bfloat16"):
+        raise ValueError(f"teacher_dtype must be 'float32' or 'bfloat16', not {teacher_dtype!r}")
+    bf16_teacher = {"inference_dtype": "bfloat16"} if teacher_dtype == "bfloat16" else {}  # float32: built as it always was
     vit = PretrainedViTWrapper(args.model, stride=args.stride_size, checkpoint_path=args.vit_checkpoint,
-                               img_size=args.input_size, allow_random_init=args.allow_random_vit, dtype="float32")
+                               img_size=args.input_size, allow_random_init=args.allow_random_vit, dtype=teacher_dtype)
     den_sd = torch.load(args.denoiser_ckpt, map_location="cpu", weights_only=False)["denoiser"]
     teacher = Denoiser(*teacher_grid(den_sd, dim, gh, gw), feat_dim=dim, vit=vit, enable_pe="pos_embed" in den_sd,
-                       num_blocks=args.num_blocks, device=device)
+                       num_blocks=args.num_blocks, device=device, **bf16_teacher)
     teacher.load_state_dict(den_sd, strict=False)
     # the wrapper keeps the checkpoint's table un-resampled: its grid is what the student trains
     g0 = square_grid(vit._state_dict["pos_embed"].shape[-2] - SPECS[args.model].pos_has_cls, "the ViT checkpoint's pos_embed")
@@ -374,6 +385,9 @@ def train(args, rank: int, world: int, device: torch.device, model_factory=None)
         print(f"stage 3: student attention {args.attention}"
               + (" (bf16 flash attention: fp32 accumulation, probabilities recomputed in the backward pass, none kept)"
                  if args.attention == "bfloat16" else " (fp32 products, probabilities kept)"), flush=True)
+        print(f"stage 3: teacher dtype {getattr(args, 'teacher_dtype', 'float32')}"
+              + (" (bf16 extractor with the denoiser fused behind it)"
+                 if getattr(args, "teacher_dtype", "float32") == "bfloat16" else " (exact fp32 extractor and denoiser)"), flush=True)
         if getattr(args, "weight_grad", "float32") == "bfloat16":
             print("stage 3: student weight gradients bfloat16 (bf16 operands on the split-K kernel, fp32 accumulation; bias "
                   "gradients fp32)", flush=True)

@@ -87,7 +87,8 @@ int dvt_parts_gelu(const float* h, float* a, int64_t n4, int backward, void* str
 /* backward 0: S [rows][Tp] -> softmax(scale S) over keys < T in place, query rows (row % Tp) >= T and keys >= T zero (P unused);
  * backward 1: S = scale P (.) (S - rowsum(P (.) S)) in place.  Tp % 4 == 0 */
 int dvt_parts_softmax(const float* P, float* S, int T, int Tp, int64_t rows, float scale, int backward, void* stream);
-/* loss_rows<add>: dout [R][C], loss_out[4] = {l2 + 1 - cos, l2, 1 - cos, 0}, out (may be NULL) packed; acc: 64 floats of scratch.
+/* loss_rows<add>: dout [R][C], loss_out[4] = {l2 + 1 - cos, l2, 1 - cos, 0}, out (may be NULL) packed; acc: 64 floats of scratch, 8-byte
+ * aligned (the two sums are added as 128-bit integers, in any order to the same bits).
  * target / out packed [R / Tp][T - n_prefix][C]; b is read with add only */
 int dvt_parts_loss_rows(int C, const float* a, const float* b, const float* target, float* out, float* dout, float* acc,
                         int n_prefix, int T, int Tp, int R, int norm_batch, float* loss_out, int add, void* stream);

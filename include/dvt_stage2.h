@@ -76,6 +76,23 @@ int dvt_s2_train_step(const DvtS2Config* cfg, const float* params, float* grads,
                       const float* target, float* pred, int batch, void* work, int64_t work_bytes,
                       float* loss_out, void* stream);
 
+/* The training step with opt-in bf16 matrix operands.  gemm_mode is the stage-3 step's bit set
+ * (dvt_stage3.h): 1 = the forward and data-gradient GEMMs of each block's qkv / proj / fc1 / fc2 take bf16 operands (fp32
+ * accumulation, fp32 outputs); 2 = the attention is the bf16 flash attention, which keeps a log-sum-exp per row instead of
+ * the two [batch * heads, tokens_pad, tokens_pad] fp32 matrices, and leaves the k third of each qkv bias gradient untouched
+ * (it is identically zero in exact arithmetic); 4 = the weight gradients are dW = bf16(dy)^T bf16(x) on the split-K
+ * kernel, bias gradients from the unrounded dy.  Bits 2 and 4 are built on bit 1: the accepted values are 0, 1, 3, 5, 7,
+ * anything else is DVT_E_BADARG (-1 from the workspace function).  What is rounded, and where, is what DESIGN section 18
+ * states for the stage-3 step; parameters, gradients, moments, LayerNorm, GELU, the loss and the pos_embed gradient stay
+ * fp32.  Mode 0 IS dvt_s2_workspace_bytes / dvt_s2_train_step: same workspace, same carving, same launches.  The other
+ * modes need tokens_pad % 128 == 0 and mlp_dim % 128 == 0 and 16-byte aligned `params` and `work` (DVT_E_BADARG before
+ * any launch otherwise), train only (training == 0 with a mode is refused), and carve their pieces behind everything
+ * mode 0 carves.  dvt_s2_forward has no mode: bf16 inference is the extractor's (dvt_denoiser.h). */
+int64_t dvt_s2_workspace_bytes_mp(const DvtS2Config* cfg, int batch, int training, int gemm_mode);
+int dvt_s2_train_step_mp(const DvtS2Config* cfg, const float* params, float* grads, const float* x,
+                         const float* target, float* pred, int batch, void* work, int64_t work_bytes,
+                         float* loss_out, void* stream, int gemm_mode);
+
 /* torch.optim.AdamW, one step over a flat arena of n floats (n % 4 == 0):
  *   g *= grad_scale (1 / world_size after a SUM all-reduce);  p *= 1 - lr * weight_decay;
  *   m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;

@@ -11,6 +11,14 @@ student's step) is not part of the timed step.
     python tools/bench_stage3.py [--dim 768 --depth 12 --img 518 --batch 64 --steps 3 --warmup 1]
                                  [--input_size H W] [--stride_size S] [--pos_grid G0]
                                  [--dtype float32|bfloat16] [--attention float32|bfloat16] [--weight_grad float32|bfloat16] [--ab N]
+                                 [--teacher none|float32|bfloat16]
+
+`--teacher float32|bfloat16` (default none: the student alone, the output as it always was): a stage-3 ITERATION -- the
+teacher's forward (`Denoiser` over a `PretrainedViTWrapper` of that dtype with random weights, as `stage3.build_models` builds
+it for --teacher_dtype) producing the target, then the student's step against it.  With `--ab` every leg's timed unit is
+teacher + student, the teacher timed on its own inside it; the JSON line gains `teacher_ms` (median, min, max over all timed
+iterations) and per leg `iteration_ms`.  Without `--ab` it gains `teacher_ms` and `iteration_ms` of the one mode.  Needs the
+ViT-B/14 or ViT-S/14 geometry (`--dim 768 --depth 12` or `--dim 384 --depth 12`) at stride 14 without --pos_grid.
 
 `--ab N`: an interleaved A/B of the three arithmetics in one process on one engine -- fp32 step, bf16 step, bf16 step with
 bf16 attention, fp32 step, ... N of each after the warm-up of all, every step timed on its own (device synchronised on both
@@ -52,6 +60,21 @@ def step_flops(cfg, batch):
     return 3 * (patch + cfg.depth * block) - 2 * R * C * cfg.k_patch  # no data gradient for the image
 
 
+def build_teacher(a, cfg, H, W, dev):
+    """`Denoiser` over a `PretrainedViTWrapper` with random weights, as stage3.build_models builds the teacher."""
+    import warnings
+    from dvt_amd.models import Denoiser, PretrainedViTWrapper
+    from dvt_amd.vit import SPECS
+    name = {768: "vit_base_patch14_dinov2.lvd142m", 384: "vit_small_patch14_dinov2.lvd142m"}.get(a.dim)
+    if name is None or SPECS[name].depth != a.depth or a.pos_grid is not None:
+        raise SystemExit("--teacher needs --dim 768 or 384 with --depth 12 and no --pos_grid")
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        vit = PretrainedViTWrapper(name, stride=a.stride_size, img_size=(H, W), allow_random_init=True, dtype=a.teacher)
+    kw = {"inference_dtype": "bfloat16"} if a.teacher == "bfloat16" else {}
+    return Denoiser(cfg.grid_h, cfg.grid_w, feat_dim=a.dim, vit=vit, num_blocks=1, device=dev, seed=0, **kw)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--dim", type=int, default=768)
@@ -68,6 +91,8 @@ def main():
     p.add_argument("--weight_grad", default="float32", choices=["float32", "bfloat16"], help="bfloat16 needs --dtype bfloat16")
     p.add_argument("--ab", type=int, default=0, metavar="N",
                    help="interleaved fp32 / bf16 / bf16 + bf16 attention A/B, N timed steps of each")
+    p.add_argument("--teacher", default="none", choices=["none", "float32", "bfloat16"],
+                   help="time the teacher's forward of that dtype in front of every student step (an iteration)")
     p.add_argument("--pos_grid", type=int, default=None,
                    help="grid of the position table when it is not the run's (resampled in every step); default: the run's")
     a = p.parse_args()
@@ -82,6 +107,26 @@ def main():
     tgt = torch.randn(a.batch, cfg.grid_h, cfg.grid_w, a.dim, device=dev, generator=g)
     mb = a.micro_batch or None
     fl = step_flops(cfg, a.batch)
+    teacher = build_teacher(a, cfg, H, W, dev) if a.teacher != "none" else None
+    t_ms = []
+
+    def target(timed):
+        """The iteration's target: the teacher's denoised features (its forward timed on its own), or the random one."""
+        if teacher is None:
+            return tgt
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            out = teacher(img, return_dict=True)["denoised_feats"].contiguous()
+        torch.cuda.synchronize()
+        if timed:
+            t_ms.append((time.perf_counter() - t0) * 1e3)
+        return out
+
+    def stats(v):
+        v = sorted(v)
+        med = v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
+        return {"median_ms": round(med, 2), "min_ms": round(v[0], 2), "max_ms": round(v[-1], 2)}
     head = {"bench": "stage3_student_step", "dim": a.dim, "depth": a.depth, "img": a.img if a.input_size is None else [H, W],
             "stride": a.stride_size, "grid": [cfg.grid_h, cfg.grid_w], "pos_grid": a.pos_grid, "batch": a.batch}
     if a.ab > 0:
@@ -91,6 +136,7 @@ def main():
         modes = {"float32": ("float32", "float32"), "bfloat16": ("bfloat16", "float32"),
                  "bfloat16_attn": ("bfloat16", "bfloat16"), "bfloat16_attn_wgrad": ("bfloat16", "bfloat16", "bfloat16")}
         ms = {name: [] for name in modes}
+        it_ms = {name: [] for name in modes}
         per_image = {}
         for name, mode in modes.items():
             eng.set_dtype(*mode)
@@ -99,12 +145,16 @@ def main():
             for dtype, mode in modes.items():
                 eng.set_dtype(*mode)
                 torch.cuda.synchronize()
+                t_it = time.perf_counter()
+                tg = target(i >= a.warmup)
+                torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                loss = eng.train_step(img, tgt, micro_batch=mb)
+                loss = eng.train_step(img, tg, micro_batch=mb)
                 eng.adamw_step(1e-5, 1e-5)
                 torch.cuda.synchronize()
                 if i >= a.warmup:
                     ms[dtype].append((time.perf_counter() - t0) * 1e3)
+                    it_ms[dtype].append((time.perf_counter() - t_it) * 1e3)
         legs = {}
         for dtype, v in ms.items():
             v = sorted(v)
@@ -112,6 +162,10 @@ def main():
             legs[dtype] = {"median_ms": round(med, 2), "min_ms": round(v[0], 2), "max_ms": round(v[-1], 2),
                            "images_per_s": round(a.batch / med * 1e3, 2), "tflops": round(fl / med / 1e9, 2),
                            "workspace_bytes_per_image": per_image[dtype]}
+            if teacher is not None:
+                legs[dtype]["iteration_ms"] = stats(it_ms[dtype])
+        if teacher is not None:
+            head = {**head, "teacher": a.teacher, "teacher_ms": stats(t_ms)}
         f32, b16, att, wg = legs["float32"], legs["bfloat16"], legs["bfloat16_attn"], legs["bfloat16_attn_wgrad"]
         print(json.dumps({**head, "mode": "interleaved_ab", "steps_each": a.ab, "slice": mb, "tflop_per_step": round(fl / 1e12, 2),
                           "float32": f32, "bfloat16": b16, "bfloat16_attn": att, "bfloat16_attn_wgrad": wg,
@@ -130,15 +184,19 @@ def main():
                           "loss": float(loss[0].cpu())}), flush=True)
         return
     for _ in range(a.warmup):
-        eng.train_step(img, tgt, micro_batch=mb)
+        eng.train_step(img, target(False), micro_batch=mb)
         eng.adamw_step(1e-5, 1e-5)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        loss = eng.train_step(img, tgt, micro_batch=mb)
+        loss = eng.train_step(img, target(True), micro_batch=mb)
         eng.adamw_step(1e-5, 1e-5)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
+    if teacher is not None:  # the timed loop held the teacher too: the student's share is what is left
+        it = dt * 1e3
+        dt -= sum(t_ms) / len(t_ms) / 1e3
+        head = {**head, "teacher": a.teacher, "teacher_ms": stats(t_ms), "iteration_ms": round(it, 2)}
     print(json.dumps({**head, "dtype": a.dtype, "attention": a.attention, "weight_grad": a.weight_grad,
                       "slice": eng.slice_size(a.batch) if mb is None else mb, "ms_per_step": round(dt * 1e3, 2),
                       "images_per_s": round(a.batch / dt, 3), "tflop_per_step": round(fl / 1e12, 2),
